@@ -11,19 +11,33 @@ scaling: weak — every rank processes its own 64 slabs (sharding over
          batch × head, no data-path collective; a barrier and a MAX
          all-reduce of the elapsed time are the only cross-rank calls).
 
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does only what the
+headline figure needs: set up, settle, W warm-up steps, the K timed steps, the
+optional output dump, and the JSON line.  Everything else listed below runs
+with --full.
+
 Timing protocol:
   1. settle: the step is launched back-to-back, untimed, until >= --settle-ms of
      wall time has passed (default 250 ms).  From idle the GPU needs ~60 ms of
      load to reach its sustained clock; the settle phase is DISCLOSED in the JSON
-     ("settle") together with the number measured without it ("cold": exactly W
-     warm-up steps, then the same K timed steps, measured first).
+     ("settle").  With --full the number measured without it is reported too
+     ("cold": exactly W warm-up steps, then the same K timed steps, measured
+     first).
   2. W untimed warm-up steps, then EXACTLY K timed steps bracketed by a barrier
      + torch.cuda.synchronize() on both sides; MAX over ranks.
-  3. the GPU clock and board power are sampled (amdsmi via torch.cuda) during
-     the timed region and reported ("clock").
+  3. with --full the GPU clock and board power are sampled (amdsmi via
+     torch.cuda) during the timed region and reported ("clock").
 
-Secondary blocks on the same JSON line (never the headline `value`), keyed by
-the BASELINE.json configs index they measure:
+--dump-outputs DIR: after the timed steps, what the last timed step left in the
+arrays a caller of dense_fa_ receives is written as float32 DIR/O.npy, DIR/l.npy
+and DIR/m.npy (rank r > 0: DIR/O.rank<r>.npy ...).  l and m are whole; O is a
+fixed, seeded sample of DUMP_ROWS of its N·(B·H) rows (a row = one token's d
+outputs in one slab; the same rows every run), since the whole array as float32
+is 64 MiB.  The inputs come from a seeded generator, so two builds run with the
+same arguments can be compared output for output.
+
+Secondary blocks on the same JSON line with --full (never the headline `value`),
+keyed by the BASELINE.json configs index they measure:
   * "cfg2": configs[2] = windowed_fa 2-D bf16, 128x128 image, ws 7, d 64:
     forward and backward at B = 1 (as written) and B = 32, GB/s against the
     8 TB/s HBM roofline (HIP-graph replay: launch-bound at B = 1);
@@ -41,7 +55,8 @@ the BASELINE.json configs index they measure:
     published Float64 case (512, 64, 1) likewise, and the whole configs[1]
     workload (fp32).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu] [--no-cfg4] [--no-cfg23] [--extra]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+                       [--full [--no-cpu] [--no-cfg4] [--no-cfg23] [--extra]]
 Multi-GPU: `python bench.py --gpus N` (N > 1, WORLD_SIZE unset) starts N ranks
            itself as a child `python -m torch.distributed.run --nnodes=1
            --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...`
@@ -247,6 +262,25 @@ def _randn_jl(fa, shape, dtype, gen):
     t = fa.jl_empty(shape, dtype)
     t.normal_(generator=gen)
     return t
+
+
+DUMP_ROWS = 1 << 17    # of configs[1]'s N·(B·H) = 2^18 rows of O: 32 MiB as float32
+DUMP_SEED = 20240      # picks the rows: the same ones every run
+
+
+def dump_outputs(path, rank, O, l, m):
+    """--dump-outputs: the arrays the last dense_fa_ call filled, as float32 .npy.
+    l, m (N, 1, B·H) whole; of O (N, d, B·H) the rows picked by a fixed seed, in
+    ascending (slab, token) order: O.npy[i] = O[r % N, :, r // N], r = rows[i]."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    N, d, BH = O.shape
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(N * BH, size=min(DUMP_ROWS, N * BH), replace=False))
+    idx = torch.from_numpy(rows).to(O.device)
+    o_rows = O.permute(2, 0, 1).reshape(BH * N, d).index_select(0, idx)
+    sfx = "" if rank == 0 else f".rank{rank}"
+    for name, t in (("O", o_rows), ("l", l), ("m", m)):
+        np.save(os.path.join(path, f"{name}{sfx}.npy"), np.ascontiguousarray(t.float().cpu().numpy()))
 
 
 def cfg4_block(fa, world, rank, dist, steps, warmup, cpu_hook=False):
@@ -475,7 +509,7 @@ def cpu_baseline(node: bool = False):
     tile product, (slab x row-block) tasks), fp32.
       * default leg "share": the box's per-GPU OMP_NUM_THREADS share (16 on the GPU
         box; the harness asks GPU jobs to keep their worker pools to it) -> `value`;
-      * node=True (bench.py --cpu-node) adds the node's host cores, every CPU of the
+      * node=True (bench.py --full --cpu-node) adds the node's host cores, every CPU of the
         affinity set (north_star): "node_blas" = the BLAS port at min(CPUs, 64)
         threads (numpy's OpenBLAS build limit), "node_plain" = the same algorithm
         without BLAS on all CPUs; `value` / `cores` then come from the faster leg.
@@ -533,7 +567,7 @@ def cpu_baseline(node: bool = False):
                       f"(oracle/fa_cpu.c: Br=64 Bc=500 tiles), leg '{best}': {bl['impl']} at {bl['threads']} "
                       f"threads, median of 3: {bl['configs1_s']:.3f} s; 'legs' adds configs[0] and the "
                       f"reference's Float64 case" + ("" if node else
-                      f"; the node-wide legs (all {ncpu} affinity CPUs) run with bench.py --cpu-node "
+                      f"; the node-wide legs (all {ncpu} affinity CPUs) run with bench.py --full --cpu-node "
                       f"(profiles/r04_cpu_baseline_node.log: slower than this leg, since the job's "
                       f"cgroup quota is {_cpu_quota()} CPUs)"),
             "legs": legs,
@@ -580,6 +614,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--settle-ms", type=float, default=250.0,
                     help="untimed back-to-back launches before timing (disclosed in the JSON)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as float32 DIR/<name>.npy (O: a seeded row sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the cold number, clock sampling, the "
+                         "configs[2] / [3] / [4] blocks, --extra and the CPU baseline (the options below)")
     ap.add_argument("--cfg4-steps", type=int, default=3)
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--cpu-node", action="store_true",
@@ -629,14 +668,18 @@ def main():
         sync, events = _cuda_sync, True
     BH = B_ * H_
     flops_rank = 4.0 * BH * N_ * N_ * D_
-    sampler = (lambda: _NullSampler()) if cpu_hook else (lambda: ClockSampler(torch.cuda.current_device()))
+    sampler = ((lambda: _NullSampler()) if cpu_hook or not args.full
+               else (lambda: ClockSampler(torch.cuda.current_device())))
 
-    # cold: exactly W warm-up steps from idle, then the K timed steps
-    wall_c, ev_c = time_region(step, args.steps, args.warmup, dist, sync, events)
+    if args.full:
+        # cold: exactly W warm-up steps from idle, then the K timed steps
+        wall_c, ev_c = time_region(step, args.steps, args.warmup, dist, sync, events)
     with sampler() as clk_settle:   # sustained load: many samples
         settle_n, settle_s = settle(step, (0.0 if cpu_hook else args.settle_ms) / 1e3, sync)
     with sampler() as clk:
         wall, ev_s = time_region(step, args.steps, args.warmup, dist, sync, events)
+    if args.dump_outputs and not cpu_hook:
+        dump_outputs(args.dump_outputs, rank, O, l, m)
     value = flops_rank * world * args.steps / wall / 1e12
     kern_s = ev_s / args.steps
     achieved = flops_rank / kern_s / 1e12
@@ -655,38 +698,42 @@ def main():
                      "flops_per_launch": flops_rank, "avg_launch_ms": kern_s * 1e3},
         "settle": {"ms": settle_s * 1e3, "launches": settle_n,
                    "why": "untimed back-to-back launches so the GPU leaves its idle clock (DESIGN.md §6)"},
-        "cold": {"value": flops_rank * world * args.steps / wall_c / 1e12,
-                 "avg_launch_ms": ev_c / args.steps * 1e3,
-                 "what": "the same K steps after exactly W warm-up steps from idle, measured before settle"},
-        "clock": clk.summary(),
+        "full": args.full,
+    }
+    if args.dump_outputs and not cpu_hook:
+        out["dump_outputs"] = os.path.abspath(args.dump_outputs)
+    if cpu_hook:
+        out["cpu_step_hook"] = True
+    if args.full:
+        out["cold"] = {"value": flops_rank * world * args.steps / wall_c / 1e12,
+                       "avg_launch_ms": ev_c / args.steps * 1e3,
+                       "what": "the same K steps after exactly W warm-up steps from idle, measured before settle"}
+        out["clock"] = clk.summary()
         # the timed region lasts a few ms, which holds one or two amdsmi samples (and the
         # power reading averages over a longer window): the settle phase just before it
         # runs the same launches back to back for --settle-ms and is sampled throughout
-        "clock_settle": clk_settle.summary(),
-    }
-    if cpu_hook:
-        out["cpu_step_hook"] = True
+        out["clock_settle"] = clk_settle.summary()
 
-    # configs[2] (HBM-bound, microseconds per call) before the d = 128 blocks, whose
-    # sustained 1400-W load would otherwise set the clock it is timed at
-    if not (args.no_cfg23 or args.no_cfg2) and not cpu_hook:
-        out["cfg2"] = cfg2_block(fa_hip, dist)
-    if not (args.no_cfg23 or args.no_cfg3) and not cpu_hook:
-        out["cfg3"] = cfg3_block(fa_hip, dist, settle_s=args.settle_ms / 1e3)
-        if shared_gpu:
-            # co-tenant ranks: the single pass needs no co-residency (every hand-off wait
-            # is on an earlier-dispatched workgroup), so it stays the plan here too
-            out["cfg3"]["bwd_plan"] = "single pass: the ranks share one GPU"
-    if not args.no_cfg4:
-        out["cfg4"] = cfg4_block(fa_hip, world, rank, dist, args.cfg4_steps, 1, cpu_hook)
+        # configs[2] (HBM-bound, microseconds per call) before the d = 128 blocks, whose
+        # sustained 1400-W load would otherwise set the clock it is timed at
+        if not (args.no_cfg23 or args.no_cfg2) and not cpu_hook:
+            out["cfg2"] = cfg2_block(fa_hip, dist)
+        if not (args.no_cfg23 or args.no_cfg3) and not cpu_hook:
+            out["cfg3"] = cfg3_block(fa_hip, dist, settle_s=args.settle_ms / 1e3)
+            if shared_gpu:
+                # co-tenant ranks: the single pass needs no co-residency (every hand-off wait
+                # is on an earlier-dispatched workgroup), so it stays the plan here too
+                out["cfg3"]["bwd_plan"] = "single pass: the ranks share one GPU"
+        if not args.no_cfg4:
+            out["cfg4"] = cfg4_block(fa_hip, world, rank, dist, args.cfg4_steps, 1, cpu_hook)
 
-    if args.extra and not cpu_hook:
-        out["extra"] = extra_benches(fa_hip, args, dist)
+        if args.extra and not cpu_hook:
+            out["extra"] = extra_benches(fa_hip, args, dist)
 
-    if rank == 0 and world == 1 and not args.no_cpu and not cpu_hook:
-        out["cpu_baseline"] = cpu_baseline(node=args.cpu_node)
-    elif rank == 0:
-        out["cpu_baseline"] = None
+        if rank == 0 and world == 1 and not args.no_cpu and not cpu_hook:
+            out["cpu_baseline"] = cpu_baseline(node=args.cpu_node)
+        elif rank == 0:
+            out["cpu_baseline"] = None
     if rank == 0:
         print(json.dumps(out), flush=True)
     if dist is not None:

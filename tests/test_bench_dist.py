@@ -109,9 +109,10 @@ def test_bench_gpus_2_literal_command_spawns_two_ranks():
     """The driver's literal form `python bench.py --gpus 2` (no torch.distributed.run
     around it) starts two ranks itself; with the CPU step hook (rank r sleeps
     (r + 1) * 5 ms per step) the JSON line must say n_gpus 2, split configs[4]'s 1024
-    slabs as [[0, 512], [512, 1024]] and report the MAX over ranks (the slow rank)."""
+    slabs as [[0, 512], [512, 1024]] (a --full block) and report the MAX over ranks
+    (the slow rank)."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4",
-                        "--warmup", "1", "--cfg4-steps", "2", "--no-cpu"],
+                        "--warmup", "1", "--full", "--cfg4-steps", "2", "--no-cpu"],
                        cwd=ROOT, env=_bench_env(), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -129,6 +130,35 @@ def test_bench_gpus_2_literal_command_spawns_two_ranks():
     # aggregate over both ranks: value = world * per-rank FLOPs / the slowest rank's time
     flops_rank = 4.0 * 64 * 4096 * 4096 * 64
     assert abs(out["value"] - 2 * flops_rank * 4 / (out["ms_per_step"] * 4 / 1e3) / 1e12) < 1e-6 * out["value"]
+
+
+@_cpu_only
+@pytest.mark.parametrize("full", [False, True])
+def test_plain_run_measures_the_headline_only(full, monkeypatch, capsys):
+    """`bench.py --gpus 1 --steps K --warmup W` times exactly K steps (the CPU step
+    hook: 5 ms each) and reports nothing beside the headline figure; the cold number,
+    the secondary blocks and the CPU baseline key appear with --full."""
+    for k, v in _bench_env().items():
+        monkeypatch.setenv(k, v)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    calls = []
+    real = bench._cpu_hook_step
+    monkeypatch.setattr(bench, "_cpu_hook_step", lambda rank: (lambda s=real(rank): (calls.append(1), s())))
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2", "--cfg4-steps", "2"]
+                        + (["--full"] if full else []))
+    assert bench.main() == 0
+    out = json.loads([ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")][0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in out
+    assert out["steps"] == 3 and out["warmup"] == 2 and out["ms_per_step"] >= 5.0 and out["full"] is full
+    moved = {"cold", "clock", "clock_settle", "cfg4", "cpu_baseline"}
+    if full:
+        assert moved <= set(out)
+        assert len(calls) == 2 * (2 + 3) + (1 + 2)      # cold + headline, then configs[4]
+    else:
+        assert not (moved | {"cfg2", "cfg3", "extra"}) & set(out)
+        assert len(calls) == 2 + 3                      # W warm-up steps + K timed steps, nothing else
 
 
 @_cpu_only

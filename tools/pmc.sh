@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
 OUT=gpurun_out/pmc
 mkdir -p $OUT
-CMD="${PMC_CMD:-python3 bench.py --steps 5 --warmup 2 --no-cpu}"
+CMD="${PMC_CMD:-python3 bench.py --full --steps 5 --warmup 2 --no-cpu}"
 i=0
 for grp in "$@"; do
   i=$((i+1))
