@@ -96,6 +96,23 @@ __device__ __forceinline__ u32x4 load_chunk(const T* base, int row, int col0, in
     return u.v;
 }
 
+// {(T)(a * s), (T)(b * s)} as one dword, a in the low half.  For f16 hipcc compiles
+// (T)(x * s) to one v_fma_mixlo_f16 (the product rounded once, where a multiply and a packed
+// conversion round twice), so the pair is built from that instruction and its high-half
+// twin: the bits then match the per-element stores of every other forward path.
+template <class T>
+__device__ __forceinline__ unsigned pack_scaled(float a, float b, float s) {
+    if constexpr (std::is_same<T, f16>::value) {
+        unsigned r;
+        asm("v_fma_mixlo_f16 %0, %1, %3, 0\n\tv_fma_mixhi_f16 %0, %2, %3, 0" : "=&v"(r) : "v"(a), "v"(b), "v"(s));
+        return r;
+    } else {
+        typedef T T2 __attribute__((ext_vector_type(2)));
+        const T2 v = {(T)(a * s), (T)(b * s)};
+        return __builtin_bit_cast(unsigned, v);
+    }
+}
+
 // --------------------------------------------------------------------------
 // bf16 / fp16 forward (v_mfma_f32_32x32x16_{bf16,f16})
 // --------------------------------------------------------------------------
@@ -486,7 +503,8 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
     // tokens] image read back by transposed reads, and O leaves through the same image
     // as 16-B row stores, instead of 2-byte gathers / scatters (one per feature and
     // query).  The 32-B blocks of image row f are XOR-ed with (f & 3) | (bit 2 of f) << 2:
-    // conflict-free transposed reads (4 rows) and b16 writes (rows f, f + 4).
+    // conflict-free transposed reads (4 rows), paired b32 writes (rows f, f + 2 per 32-lane
+    // group) and b128 reads of the epilogue.
     constexpr int ROWB = BM * 2;
     constexpr int QOOFF = (2 * STAGE + 16 + 255) & ~255;
     constexpr int QOB = WIDE ? (D > DV ? D : DV) * ROWB : 0;
@@ -516,6 +534,38 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
     const auto krs = slab_rsrc((const T*)p.K + (int64_t)b * ldk * d, (uint32_t)(ldk * d * (int)sizeof(T)));
     const auto vrs = slab_rsrc((const T*)p.V + (int64_t)b * ldk * dv, (uint32_t)(ldk * dv * (int)sizeof(T)));
 
+    // The first K/V tile's loads go out before anything else (ahead of the Q image's DMA, so
+    // that they are not queued behind it); only what feeds them is computed first.
+    // Threads past the chunk count (small head dims at 8 waves) load an
+    // out-of-range offset (→ 0) and store into a scratch slot past the tile.
+    const bool kact = KTOT >= NTH || tid < KTOT, vact = VTOT >= NTH || tid < VTOT;
+    int kgo[KCH], vgo[VCH];
+#pragma unroll
+    for (int it = 0; it < KCH; ++it) {
+        const int ch = tid + NTH * it, f = ch / CPR, pc = ch % CPR;
+        kgo[it] = kact ? (f * ldk + pc * 8) * 2 : 0x7FFFFFF0;
+    }
+#pragma unroll
+    for (int it = 0; it < VCH; ++it) {
+        const int ch = tid + NTH * it, f = ch / CPR, pc = ch % CPR;
+        vgo[it] = vact ? (f * ldk + pc * 8) * 2 : 0x7FFFFFF0;
+    }
+    const int NT = (Nk + BN - 1) / BN;
+    const bool ragged = (Nk % BN) != 0;
+    // key tiles [jt0, jt1) of this workgroup (all tiles unless split-KV)
+    const int jt0 = SPLIT ? split * p.tps : 0, jt1 = SPLIT ? min(NT, jt0 + p.tps) : NT;
+
+    u32x4 kreg[KCH], vreg[VCH];
+    auto gload = [&](int j) {
+        const int kb0 = j * BN * 2;
+#pragma unroll
+        for (int it = 0; it < KCH; ++it) kreg[it] = __builtin_amdgcn_raw_buffer_load_b128(krs, kgo[it] + kb0, 0, 0);
+#pragma unroll
+        for (int it = 0; it < VCH; ++it) vreg[it] = __builtin_amdgcn_raw_buffer_load_b128(vrs, vgo[it] + kb0, 0, 0);
+    };
+    gload(jt0);
+    FA_FWD_STAMP(5);
+
     int qiv[NQB];
     F8 qf[NQB][D / 16];
     if constexpr (WIDE) {
@@ -531,6 +581,7 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
         }
 #pragma unroll
         for (int u = 0; u < NQB; ++u) qiv[u] = qb * BM + (wave * NQB + u) * 32 + r;
+        FA_FWD_STAMP(4);
     }
 #pragma unroll
     for (int u = 0; u < NQB && !WIDE; ++u) {
@@ -553,20 +604,15 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
         koff[kb] = (8 * h + qq) * KROW + (((kb * 2 + kh) ^ kswz(qq)) * 32) + 8 * sig;
     const int voff = r * VROW + 16 * h;
 
-    int kgo[KCH], kso[KCH], vgo[VCH], vso[VCH];
-    // threads past the chunk count (small head dims at 8 waves) load an
-    // out-of-range offset (→ 0) and store into a scratch slot past the tile
-    const bool kact = KTOT >= NTH || tid < KTOT, vact = VTOT >= NTH || tid < VTOT;
+    int kso[KCH], vso[VCH];
 #pragma unroll
     for (int it = 0; it < KCH; ++it) {
         const int ch = tid + NTH * it, f = ch / CPR, pc = ch % CPR;
-        kgo[it] = kact ? (f * ldk + pc * 8) * 2 : 0x7FFFFFF0;
         kso[it] = kact ? f * KROW + (((pc >> 1) ^ kswz(f)) * 32) + (pc & 1) * 16 : 2 * STAGE;
     }
 #pragma unroll
     for (int it = 0; it < VCH; ++it) {
         const int ch = tid + NTH * it, f = ch / CPR, pc = ch % CPR;
-        vgo[it] = vact ? (f * ldk + pc * 8) * 2 : 0x7FFFFFF0;
         vso[it] = vact ? f * VROW + pc * 16 : 2 * STAGE - KBYTES;
     }
 
@@ -582,17 +628,7 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
     for (int u = 0; u < NQB; ++u) { m_used[u] = kNegInf; m_true[u] = kNegInf; l_run[u] = 0.0f; }
     const float c = p.scale_log2;
     const float thr_raw = p.rescale_log2 / c;
-    const int NT = (Nk + BN - 1) / BN;
-    const bool ragged = (Nk % BN) != 0;
 
-    u32x4 kreg[KCH], vreg[VCH];
-    auto gload = [&](int j) {
-        const int kb0 = j * BN * 2;
-#pragma unroll
-        for (int it = 0; it < KCH; ++it) kreg[it] = __builtin_amdgcn_raw_buffer_load_b128(krs, kgo[it] + kb0, 0, 0);
-#pragma unroll
-        for (int it = 0; it < VCH; ++it) vreg[it] = __builtin_amdgcn_raw_buffer_load_b128(vrs, vgo[it] + kb0, 0, 0);
-    };
     auto lstore = [&](char* buf, int j) {
         if (ragged && j == NT - 1) {   // keys >= Nk read the next feature row: zero V there
 #pragma unroll
@@ -685,12 +721,11 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
 
     char* const buf0 = smem;
     char* const buf1 = smem + STAGE;
-    // key tiles [jt0, jt1) of this workgroup (all tiles unless split-KV)
-    const int jt0 = SPLIT ? split * p.tps : 0, jt1 = SPLIT ? min(NT, jt0 + p.tps) : NT;
-    gload(jt0);
-    lstore(buf0, jt0);
+    lstore(buf0, jt0);   // waits for the K/V loads only: the Q DMA issued after them is still in flight
     if constexpr (WIDE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's Q DMA landed
+    FA_FWD_STAMP(6);
     __syncthreads();
+    FA_FWD_STAMP(7);
     if constexpr (WIDE) {
 #pragma unroll
         for (int u = 0; u < NQB; ++u)
@@ -745,31 +780,61 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
     }
 
     if constexpr (WIDE) {
-        // O (normalised, T) into the Q/O image, then one 16-B store per lane and row chunk
+        // O (normalised, T) into the Q/O image as token pairs.  Lanes r and r ^ 1 hold adjacent
+        // tokens of the same features: a lane packs (feature f, feature f + 2) of its own
+        // token, swaps the pair with its neighbour (DPP quad_perm [1,0,3,2]) and writes
+        // (token r & ~1, token r | 1) of feature f (even lanes) or f + 2 (odd lanes) as one
+        // b32: half the LDS writes, and every conversion's two halves are used.  Each value is
+        // still (T)(oacc * inv) of its own token.  Rows f and f + 2 differ in bit 1 of the
+        // block XOR, so the 32 lanes of a write group cover 32 distinct banks.
+        const int odd = lane & 1;
+        const unsigned sel = odd ? 0x03020706u : 0x05040100u;   // v_perm_b32: (nb.hi, own.hi) : (own.lo, nb.lo)
 #pragma unroll
         for (int u = 0; u < NQB; ++u) {
             const int qi = qiv[u];
             const float lt = swap_halves_sum(l_run[u]);
             const float inv = 1.0f / lt;
-            const int tb = ((wave * NQB + u) * 32 + r) * 2;
+            const int tb = ((wave * NQB + u) * 32 + (r & ~1)) * 2;
+            // acc_row(4 k + e, h) = 8 k + e + 4 h (e = 0, 1); + 2 for register 4 k + e + 2
+            const int wb[2] = {qo_at(4 * h + 2 * odd, tb), qo_at(4 * h + 2 * odd + 1, tb)};
 #pragma unroll
             for (int cb = 0; cb < DV / 32; ++cb)
 #pragma unroll
-                for (int x = 0; x < 16; ++x)
-                    *(T*)(qoimg + qo_at(cb * 32 + acc_row(x, h), tb)) = (T)(oacc[u][cb][x] * inv);
+                for (int k = 0; k < 4; ++k)
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        const int x = 4 * k + e;
+                        const int ow = (int)pack_scaled<T>(oacc[u][cb][x], oacc[u][cb][x + 2], inv);
+                        const int nb = __builtin_amdgcn_mov_dpp(ow, 0xB1, 0xF, 0xF, true);
+                        *(unsigned*)(qoimg + wb[e] + (cb * 32 + 8 * k) * ROWB) =
+                            __builtin_amdgcn_perm((unsigned)nb, (unsigned)ow, sel);
+                    }
             if (qi < N && h == 0) {
                 p.m[(int64_t)b * N + qi] = m_true[u] * p.scale;
                 p.l[(int64_t)b * N + qi] = lt * exp2_fast((m_used[u] - m_true[u]) * c);
             }
         }
-        __syncthreads();
+        FA_FWD_STAMP(8);
+        // Each wave stores the 16-B chunks of its own 32 * NQB tokens (with NQB = 2 one whole
+        // 128-B line per feature row), so no other wave's image writes are read: the LDS
+        // serves one wave's instructions in order and no workgroup barrier is needed; a wave
+        // that finishes its tiles early stores and leaves.
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        FA_FWD_STAMP(9);
         const auto ors = slab_rsrc((T*)p.O + (int64_t)b * N * dv, (uint32_t)(N * dv * (int)sizeof(T)));
-        constexpr int CPRO = ROWB / 16;
-        static_assert(DV * CPRO % NTH == 0, "O image store split");
+        constexpr int TPW = 32 * NQB, CPW = TPW / 8, RPI = 64 / CPW;   // tokens, chunks per row, rows per instruction
+        static_assert(DV % RPI == 0, "O image store split");
+        const int oc = lane % CPW, rs = lane / CPW;
+        // 8 rows x 8 chunks per instruction: rows in the order 0 1 4 5 2 3 6 7, so that each
+        // 16-lane group of the b128 read covers all 16 slots of a bank row; 16 rows x 4 chunks
+        // are conflict-free in plain order
+        const int fr = NQB == 2 ? ((rs & 1) | ((rs & 2) << 1) | ((rs & 4) >> 1)) : rs;
+        const int lb = (wave * TPW + oc * 8) * 2;
+        const int q = qb * BM + wave * TPW + oc * 8;
 #pragma unroll
-        for (int it = 0; it < DV * CPRO / NTH; ++it) {
-            const int ch = it * NTH + tid, f = ch / CPRO, lb = (ch - f * CPRO) * 16;
-            const int q = qb * BM + lb / 2;
+        for (int it = 0; it < DV / RPI; ++it) {
+            const int f = it * RPI + fr;
             const u32x4 v4 = *(const u32x4*)(qoimg + qo_at(f, lb));
             // branch-free: a chunk outside (dv, N) gets an offset past the slab descriptor's
             // range, which the buffer store drops (no per-store exec-mask branch in the tail)

@@ -1,6 +1,8 @@
 """A/B the dense forward of two builds of libfa_hip.so in ONE process, interleaved
-rounds after a clock settle: configs[1] (4096, 64, 64 slabs) bf16 and a ragged-key
-shape; y, l, m checked bitwise against the first build.
+rounds after a clock settle: configs[1] (4096, 64, 64 slabs) bf16, the same with 128
+slabs, a ragged-key shape, configs[3] and configs[3] on the 8-wave kernel (variant 5,
+w8b64_wide); y, l, m checked bitwise against the first build.  Prints every round (a gain counts when every round favours it and the median
+gain exceeds the spread between rounds of one build).
 Usage: python tools/exp/ab_fwd_libs.py LIB_A LIB_B"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -21,18 +23,23 @@ def use(i):
 
 
 g = torch.Generator(device="cuda").manual_seed(1)
-shapes = [(4096, 4096, 64, 64), (4096, 4000, 64, 64), (8192, 8192, 128, 64)]
+# (N, Nk, d, slabs[, forward variant])
+shapes = [(4096, 4096, 64, 64), (4096, 4096, 64, 128), (4096, 4000, 64, 64), (8192, 8192, 128, 64), (8192, 8192, 128, 64, 5)]
+if os.environ.get("AB_SHAPES"):   # e.g. AB_SHAPES="4096,4096,64,64;8192,8192,128,64,5"
+    shapes = [tuple(int(x) for x in sh.split(",")) for sh in os.environ["AB_SHAPES"].split(";")]
 data = {}
-for (N, Nk, d, BH) in shapes:
+for (N, Nk, d, BH) in sorted(set(sh[:4] for sh in shapes)):
     data[(N, Nk, d, BH)] = (_randn_jl(fa_hip, (N, d, BH), torch.bfloat16, g), _randn_jl(fa_hip, (Nk, d, BH), torch.bfloat16, g),
                             _randn_jl(fa_hip, (Nk, d, BH), torch.bfloat16, g))
 use(0)
-Q, K, V = data[shapes[0]]
+Q, K, V = data[shapes[0][:4]]
 for _ in range(2000):
     fa_hip.dense_fa(Q, K, V)
 torch.cuda.synchronize()
 for sh in shapes:
-    Q, K, V = data[sh]
+    Q, K, V = data[sh[:4]]
+    for L in libs:
+        L.fa_debug_set_fwd_variant(sh[4] if len(sh) > 4 else 0)
     ref = None
     same = {}
     for i in range(len(libs)):
@@ -52,9 +59,13 @@ for sh in shapes:
                 fa_hip.dense_fa(Q, K, V)
             e1.record(); torch.cuda.synchronize()
             ts[i].append(e0.elapsed_time(e1) / 40 * 1e3)
-    N, Nk, d, BH = sh
+    N, Nk, d, BH = sh[:4]
     fl = 4.0 * BH * N * Nk * d
+    for i in range(len(libs)):
+        print(f"{sh} lib {i} rounds (us): " + " ".join(f"{t:.1f}" for t in ts[i]), flush=True)
     for i in range(len(libs)):
         v = sorted(ts[i])
         print(f"{sh} lib {i}: median {v[len(v) // 2]:8.1f} us  best {v[0]:8.1f}  ({fl / v[len(v) // 2] / 1e6:6.0f} TFLOP/s)  "
               f"bitwise equal to lib 0: {same[i]}", flush=True)
+for L in libs:
+    L.fa_debug_set_fwd_variant(0)

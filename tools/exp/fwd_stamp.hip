@@ -11,7 +11,7 @@
 __device__ unsigned long long g_fstamp[16 * 8192];
 #define FA_FWD_STAMP(k)                                                                               \
     do {                                                                                              \
-        if ((threadIdx.x & 255) == 0) {                                                               \
+        if ((k) < 4 && (threadIdx.x & 255) == 0) { /* phases 4..9: fwd_timeline.hip only */           \
             const int slot_ = blockIdx.x * 16 + (threadIdx.x >> 8) * 8;                               \
             ::g_fstamp[slot_ + (k)] = __builtin_amdgcn_s_memtime();                                   \
             if ((k) == 0) ::g_fstamp[slot_ + 6] = __builtin_amdgcn_s_memrealtime();                   \
