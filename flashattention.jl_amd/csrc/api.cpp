@@ -211,6 +211,10 @@ int fa_debug_set_circ_generic(int v) {
     return old;
 }
 
+// Not part of the public header: which kernel family the calling thread's last
+// fa_circulant_bwd launched: 0 none, 1 MFMA tiled, 2 SIMT, 3 Float64 (tests).
+int fa_debug_last_circ_bwd_kernel(void) { return fa::g_circ_bwd_last_kernel; }
+
 // Not part of the public header: windowed forward path override (1 composed,
 // 2 register-gather fused, 3 one-window row-shift (ws <= 7) / row-scatter, 4 four-window
 // row-scatter, 5 one-window row-scatter, 6 two-window row-shift (the auto choice at ws <= 7),
@@ -438,6 +442,31 @@ int fa_circulant_fwd(int dtype, const void* Q, const void* K, const void* V, voi
     a.scale64 = resolve_scale64(scale, d);
     const char* why = "";
     const int rc = fa::launch_circulant_fwd(a, (hipStream_t)hip_stream, &why);
+    return rc == FA_OK ? ok() : fail(rc, fn, why);
+}
+
+size_t fa_circulant_bwd_workspace(int dtype, int64_t N, int64_t d, int64_t dv, int64_t batch, int64_t W) {
+    if (!valid_dtype(dtype) || N < 1 || d < 1 || dv < 1 || batch < 1 || W < 1) return 0;
+    return fa::circulant_bwd_workspace(dtype, N, batch);
+}
+
+int fa_circulant_bwd(int dtype, const void* Q, const void* K, const void* V, const void* O, const void* dO,
+                     const float* l, const float* m, void* dQ, void* dK, void* dV, int64_t N, int64_t d,
+                     int64_t dv, int64_t batch, int64_t W, float scale, void* workspace,
+                     size_t workspace_bytes, void* hip_stream) {
+    static const char* fn = "fa_circulant_bwd";
+    if (!valid_dtype(dtype)) return fail(FA_ERR_INVALID_ARG, fn, "unknown dtype");
+    if (N < 0 || d < 1 || dv < 1 || batch < 0)
+        return fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: d, dv must be >= 1, N, batch >= 0");
+    if (W < 1) return fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: window size W must be >= 1");
+    if (N == 0 || batch == 0) return ok();   // no query, no key: no gradient element
+    if (!Q || !K || !V || !O || !dO || !l || !m || !dQ || !dK || !dV)
+        return fail(FA_ERR_INVALID_ARG, fn, "null pointer");
+    fa::CircBwdArgs a{dtype, Q, K, V, O, dO, l, m, dQ, dK, dV, N, d, dv, batch, W,
+                      resolve_scale(scale, d), workspace, workspace_bytes};
+    a.scale64 = resolve_scale64(scale, d);
+    const char* why = "";
+    const int rc = fa::launch_circulant_bwd(a, (hipStream_t)hip_stream, &why);
     return rc == FA_OK ? ok() : fail(rc, fn, why);
 }
 

@@ -78,6 +78,18 @@ struct CircArgs {
     double scale64 = 0.0;      // Float64 kernel: τ resolved in double (0: use scale)
 };
 
+struct CircBwdArgs {
+    int dtype;
+    const void *Q, *K, *V, *O, *dO;
+    const float *l, *m;
+    void *dQ, *dK, *dV;
+    int64_t N, d, dv, batch, W;
+    float scale;
+    void* workspace;
+    size_t workspace_bytes;
+    double scale64 = 0.0;      // Float64 kernels: τ resolved in double (0: use scale)
+};
+
 struct SoftmaxArgs {
     int dtype;
     const void* S;
@@ -119,6 +131,10 @@ size_t windowed_fwd_workspace(int dtype, const WindowGeom& g, int64_t d, int64_t
 int launch_windowed_fwd(const WindowedArgs& a, hipStream_t s, const char** why);
 int launch_windowed_bwd(const WindowedBwdArgs& a, hipStream_t s, const char** why);
 int launch_circulant_fwd(const CircArgs& a, hipStream_t s, const char** why);
+// circulant backward (fa_circulant_bwd.hip): checks the head dims, the 32-bit extents and
+// the workspace, in that order, before the first launch
+size_t circulant_bwd_workspace(int dtype, int64_t N, int64_t batch);
+int launch_circulant_bwd(const CircBwdArgs& a, hipStream_t s, const char** why);
 // window (unfold) / unwindow (fold, sum over overlaps) of one tensor (S..., C, B) <-> (T, C, L, B)
 int launch_window(int dtype, const void* src, void* dst, const WindowGeom& g, int64_t C, int64_t batch,
                   bool unwindow, hipStream_t s, const char** why);
@@ -152,5 +168,6 @@ extern thread_local int g_bwd_xcd;            // single pass: one XCD per slab w
 extern thread_local int g_win_force_composed; // windowed: forced path (composed / fused variants)
 extern thread_local int g_win_bwd_grid;       // windowed: strip backward workgroups (0: one per CU)
 extern thread_local int g_circ_force_generic; // circulant: forced kernel
+extern thread_local int g_circ_bwd_last_kernel; // circulant backward: family of the last launch (1 MFMA, 2 SIMT, 3 Float64)
 
 }  // namespace fa

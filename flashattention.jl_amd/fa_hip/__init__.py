@@ -39,7 +39,8 @@ __all__ = [
     "jl_empty", "jl_zeros", "jl_tensor", "jl_strides", "is_jl_contiguous",
     "dense_fa", "dense_fa_", "dense_fa_backward", "backward_handoff_status", "backward_handoff_trips",
     "windowed_fa", "block_fa",
-    "windowed_fa_backward", "window_geometry", "circulant_fa", "circulant_fa_", "circulant_dpa",
+    "windowed_fa_backward", "window_geometry", "circulant_fa", "circulant_fa_", "circulant_fa_backward",
+    "circulant_dpa",
     "fused_softmax", "fused_softmax_", "DTYPES",
 ]
 
@@ -129,6 +130,14 @@ def lib() -> ctypes.CDLL:
         L.fa_dense_fwd_workspace.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64]
     L.fa_circulant_fwd.restype = ctypes.c_int
     L.fa_circulant_fwd.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, f32, vp]
+    if hasattr(L, "fa_circulant_bwd"):
+        L.fa_circulant_bwd_workspace.restype = ctypes.c_size_t
+        L.fa_circulant_bwd_workspace.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64]
+        L.fa_circulant_bwd.restype = ctypes.c_int
+        L.fa_circulant_bwd.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                       i64, i64, i64, i64, i64, f32, vp, ctypes.c_size_t, vp]
+        L.fa_debug_last_circ_bwd_kernel.restype = ctypes.c_int
+        L.fa_debug_last_circ_bwd_kernel.argtypes = []
     L.fa_softmax_workspace.restype = ctypes.c_size_t
     L.fa_softmax_workspace.argtypes = [i64, i64, i64, ctypes.c_int]
     L.fa_softmax.restype = ctypes.c_int
@@ -335,6 +344,34 @@ def circulant_fa(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, W: int, scal
     l = jl_empty((N, 1, B), torch.float32, Q.device)
     m = jl_empty((N, 1, B), torch.float32, Q.device)
     return circulant_fa_(O, l, m, Q, K, V, W, scale)
+
+
+def circulant_fa_backward(Q, K, V, O, dO, l, m, W: int, scale: float = 0.0):
+    """Backward of :func:`circulant_fa` (the reference has none): returns
+    ``(dQ, dK, dV)`` of the band attention of query i over the keys
+    (i - p + t) mod N, t = 0..W-1.  O, l, m are the forward's outputs; all three
+    gradients are bitwise reproducible (no atomics, no sum across workgroups)."""
+    for t in (Q, K, V, O, dO, l, m):
+        _require(t.dim() == 3, "circulant_fa_backward expects 3-D (N, d, batch) arrays")
+    N, d, B = Q.shape
+    dv = V.shape[1]
+    _require(int(W) >= 1, "window size W must be >= 1")
+    _require(K.shape == (N, d, B) and V.shape == (N, dv, B), "K, V shapes disagree with Q")
+    _require(O.shape == (N, dv, B) and dO.shape == (N, dv, B), "O, dO must be (N, dv, batch)")
+    _require(l.shape == (N, 1, B) and m.shape == (N, 1, B), "l, m must be (N, 1, batch)")
+    _require(l.dtype == torch.float32 and m.dtype == torch.float32, "l, m must be float32")
+    code = _dtype_code(Q, K, V, O, dO)
+    _device_check(Q, K, V, O, dO, l, m)
+    dQ = jl_empty((N, d, B), Q.dtype, Q.device)
+    dK = jl_empty((N, d, B), Q.dtype, Q.device)
+    dV = jl_empty((N, dv, B), Q.dtype, Q.device)
+    L = lib()
+    nws = L.fa_circulant_bwd_workspace(code, N, d, dv, B, int(W))
+    ws = _workspace(Q.device, nws, entry="circulant_fa_backward")
+    _check(L.fa_circulant_bwd(code, _ptr(Q), _ptr(K), _ptr(V), _ptr(O), _ptr(dO), _ptr(l), _ptr(m),
+                              _ptr(dQ), _ptr(dK), _ptr(dV), N, d, dv, B, int(W), float(scale),
+                              _ptr(ws), int(nws), _stream(Q)))
+    return dQ, dK, dV
 
 
 def fused_softmax_(P: torch.Tensor, S: torch.Tensor, dims: int = 1) -> torch.Tensor:

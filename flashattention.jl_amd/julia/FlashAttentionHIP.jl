@@ -383,6 +383,57 @@ function circulant_fa(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3}, W::I
     return circulant_fa!(O, l, m, Q, K, V, W)
 end
 
+# circulant_fa_backward(Q, K, V, O, dO, l, m, W) — the chain rule of circulant_fa! (the
+# reference has none); O, l, m are the forward's outputs
+function circulant_fa_backward_f32(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3},
+                                   O::ROCArray{T,3}, dO::ROCArray{T,3},
+                                   l::ROCArray{Float32,3}, m::ROCArray{Float32,3}, W::Int) where {T}
+    N, d, B = size(Q)
+    dv = size(V, 2)
+    W >= 1 || throw(DimensionMismatch("window size W must be >= 1"))
+    size(K) == (N, d, B) && size(V) == (N, dv, B) ||
+        throw(DimensionMismatch("K, V shapes disagree with Q"))
+    size(O) == (N, dv, B) && size(dO) == (N, dv, B) ||
+        throw(DimensionMismatch("O, dO must be (N, dv, batch)"))
+    size(l) == (N, 1, B) && size(m) == (N, 1, B) ||
+        throw(DimensionMismatch("l, m must be (N, 1, batch)"))
+    dQ, dK, dV = similar(Q), similar(K), similar(V)
+    nws = ccall((:fa_circulant_bwd_workspace, libfa_hip), Csize_t,
+                (Cint, Int64, Int64, Int64, Int64, Int64), fa_dtype(T), N, d, dv, B, W)
+    with_workspace(nws) do ws
+        fa_check(ccall((:fa_circulant_bwd, libfa_hip), Cint,
+                       (Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float32},
+                        Ptr{Float32}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+                        Int64, Int64, Int64, Int64, Int64, Cfloat, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+                       fa_dtype(T), Q, K, V, O, dO, l, m, dQ, dK, dV, N, d, dv, B, W, 0f0,
+                       ws, nws, stream_ptr()))
+    end
+    return dQ, dK, dV
+end
+
+# Float32 statistics as the C ABI takes them, or l, m in another element type (the
+# reference's `similar(Q, N, 1, B)`), staged in Float32 as circulant_fa_staged! does
+function circulant_fa_backward(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3},
+                               O::ROCArray{T,3}, dO::ROCArray{T,3},
+                               l::ROCArray{Float32,3}, m::ROCArray{Float32,3}, W::Int) where {T}
+    return circulant_fa_backward_f32(Q, K, V, O, dO, l, m, W)
+end
+function circulant_fa_backward(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3},
+                               O::ROCArray{T,3}, dO::ROCArray{T,3},
+                               l::ROCArray{T,3}, m::ROCArray{T,3}, W::Int) where {T}
+    return circulant_fa_backward_f32(Q, K, V, O, dO, Float32.(l), Float32.(m), W)
+end
+function circulant_fa_backward(Q::ROCArray{Float32,3}, K::ROCArray{Float32,3}, V::ROCArray{Float32,3},
+                               O::ROCArray{Float32,3}, dO::ROCArray{Float32,3},
+                               l::ROCArray{Float32,3}, m::ROCArray{Float32,3}, W::Int)
+    return circulant_fa_backward_f32(Q, K, V, O, dO, l, m, W)
+end
+function circulant_fa_backward(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3},
+                               O::ROCArray{T,3}, dO::ROCArray{T,3},
+                               l::ROCArray{S,3}, m::ROCArray{S,3}, W::Int) where {T,S}
+    return circulant_fa_backward_f32(Q, K, V, O, dO, Float32.(l), Float32.(m), W)
+end
+
 # fused_softmax!(P, S; dims) — replaces src/fused_softmax.jl:10-15 (and the CUDA
 # versions src/cuda/fused_softmax.jl) for device arrays; P may be S
 function fused_softmax!(P::ROCArray{T,3}, S::ROCArray{T,3}; dims=1) where {T}

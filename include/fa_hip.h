@@ -220,6 +220,33 @@ int fa_circulant_fwd(int dtype, const void* Q, const void* K, const void* V,
                      int64_t N, int64_t d, int64_t dv, int64_t batch, int64_t W,
                      float scale, void* hip_stream);
 
+/* Workspace bytes fa_circulant_bwd needs: the per-query row statistics (two
+ * float arrays of N·batch, double for FA_DTYPE_F64), each rounded up to 256 B,
+ * plus 256 B of slack so the workspace may start at any address. */
+size_t fa_circulant_bwd_workspace(int dtype, int64_t N, int64_t d, int64_t dv,
+                                  int64_t batch, int64_t W);
+
+/* Circulant backward (the reference has none): the chain rule of
+ * fa_circulant_fwd over the same band, j(i, t) = (i - p + t) mod N:
+ *   P_it = exp(scale q_i.k_j - m_i)/l_i, dP_it = dO_i.v_j, D_i = dO_i.O_i,
+ *   dS_it = P_it (dP_it - D_i), dQ_i = scale sum_t dS_it k_j,
+ *   dK_j = scale sum_{(i,t)->j} dS_it q_i, dV_j = sum_{(i,t)->j} P_it dO_i.
+ * W > N repeats keys; every band entry counts once.  O, l, m are the forward's
+ * outputs (FA_DTYPE_F64 recomputes the row statistics in double and does not
+ * read l, m).  dQ, dK, dV are fully written, without atomics, and all three
+ * are bitwise reproducible: no sum crosses a workgroup.  N == 0 or batch == 0
+ * is a no-op.  Head dims above fa_max_head_dim() and extents past the kernels'
+ * 32-bit addressing give FA_ERR_UNSUPPORTED, a missing or short workspace
+ * FA_ERR_WORKSPACE, both before any launch. */
+int fa_circulant_bwd(int dtype,
+                     const void* Q, const void* K, const void* V,
+                     const void* O, const void* dO,
+                     const float* l, const float* m,
+                     void* dQ, void* dK, void* dV,
+                     int64_t N, int64_t d, int64_t dv, int64_t batch, int64_t W,
+                     float scale, void* workspace, size_t workspace_bytes,
+                     void* hip_stream);
+
 /* Standalone fused softmax, replaces
  *   fused_softmax!(P, S; dims)   reference src/fused_softmax.jl:1-41
  * (device versions src/cuda/fused_softmax.jl:11-314).  S, P: (M, N, batch)
