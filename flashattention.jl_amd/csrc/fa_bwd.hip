@@ -22,7 +22,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "fa_common.h"
+#include "fa_bwd_common.h"
 #include "fa_internal.h"
 #include "../../include/fa_hip.h"
 
@@ -87,8 +87,6 @@ struct BwdParams {
     const unsigned* fin = nullptr;             // ... those with fin[b][t] == 2
 };
 
-template <class T> __device__ __forceinline__ float to_f(T x) { return (float)x; }
-
 constexpr unsigned kBwdHdrMagic = 0x46414200u;   // "FAB\0"
 constexpr size_t kBwdHdrBytes = 256;
 
@@ -115,7 +113,7 @@ __global__ __launch_bounds__(256) void bwd_prepass(BwdParams p) {
     const T* O = (const T*)p.O + b * (int64_t)p.N * p.dv + n;
     const T* dO = (const T*)p.dO + b * (int64_t)p.N * p.dv + n;
     float acc = 0.0f;
-    for (int c = 0; c < p.dv; ++c) acc = fmaf(to_f(dO[(int64_t)c * p.N]), to_f(O[(int64_t)c * p.N]), acc);
+    for (int c = 0; c < p.dv; ++c) acc = fmaf((float)dO[(int64_t)c * p.N], (float)O[(int64_t)c * p.N], acc);
     p.nD[idx] = -acc;
     p.nlse[idx] = -(p.m[idx] + logf(p.l[idx])) / p.scale;
 }
@@ -126,43 +124,10 @@ __global__ __launch_bounds__(256) void bwd_prepass(BwdParams p) {
 // configs[3]).
 template <class T>
 __global__ __launch_bounds__(256) void bwd_prepass_v(BwdParams p) {
-    constexpr int U = 8;
     const int64_t g8 = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (g8 >= (int64_t)p.N * p.batch / 8) return;
     if (g8 == 0) write_bwd_header(p);
-    const int64_t idx = g8 * 8, b = idx / p.N, n = idx - b * p.N;
-    const T* O = (const T*)p.O + b * (int64_t)p.N * p.dv + n;
-    const T* dO = (const T*)p.dO + b * (int64_t)p.N * p.dv + n;
-    float acc[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) acc[k] = 0.0f;
-    auto fma8 = [&](const u32x4& a, const u32x4& c) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const unsigned wa = a[k], wc = c[k];
-            acc[2 * k] = fmaf(to_f(__builtin_bit_cast(T, (unsigned short)(wa & 0xFFFFu))),
-                              to_f(__builtin_bit_cast(T, (unsigned short)(wc & 0xFFFFu))), acc[2 * k]);
-            acc[2 * k + 1] = fmaf(to_f(__builtin_bit_cast(T, (unsigned short)(wa >> 16))),
-                                  to_f(__builtin_bit_cast(T, (unsigned short)(wc >> 16))), acc[2 * k + 1]);
-        }
-    };
-    int c = 0;
-    for (; c + U <= p.dv; c += U) {
-        u32x4 ro[U], rd[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            ro[u] = *(const u32x4*)(O + (int64_t)(c + u) * p.N);
-            rd[u] = *(const u32x4*)(dO + (int64_t)(c + u) * p.N);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) fma8(rd[u], ro[u]);
-    }
-    for (; c < p.dv; ++c) fma8(*(const u32x4*)(dO + (int64_t)c * p.N), *(const u32x4*)(O + (int64_t)c * p.N));
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        p.nD[idx + k] = -acc[k];
-        p.nlse[idx + k] = -(p.m[idx + k] + logf(p.l[idx + k])) / p.scale;
-    }
+    prepass_rows8((const T*)p.O, (const T*)p.dO, p.l, p.m, p.nD, p.nlse, g8 * 8, p.N, p.dv, p.scale);
 }
 
 // --------------------------------------------------------------------------
@@ -173,17 +138,6 @@ __global__ __launch_bounds__(256) void bwd_prepass_v(BwdParams p) {
 // --------------------------------------------------------------------------
 constexpr int kGT = 32;          // tile edge
 constexpr int kGThreads = 256;
-
-__device__ __forceinline__ float fma_a(float a, float b, float c) { return fmaf(a, b, c); }
-__device__ __forceinline__ double fma_a(double a, double b, double c) { return fma(a, b, c); }
-__device__ __forceinline__ float exp2_a(float x) { return exp2f(x); }
-__device__ __forceinline__ double exp2_a(double x) { return exp2(x); }
-template <class A> __device__ __forceinline__ A bscale(const BwdParams& p) {
-    if constexpr (sizeof(A) == 8) return p.scale64; else return p.scale;
-}
-template <class A> __device__ __forceinline__ A bscale_log2(const BwdParams& p) {
-    if constexpr (sizeof(A) == 8) return p.scale64 * 1.4426950408889634074; else return p.scale_log2;
-}
 
 // dQ: one block per (b, 32-query tile).
 template <class T, class A>
@@ -218,7 +172,7 @@ __global__ __launch_bounds__(kGThreads) void bwd_generic_dq(BwdParams p) {
     for (int t = 0; t < kMaxPer; ++t) acc[t] = (A)0;
     const A* nD = (const A*)p.nD + (int64_t)b * N;
     const A* nL = (const A*)p.nlse + (int64_t)b * N;
-    const A sl2 = bscale_log2<A>(p);
+    const A sl2 = scale_log2_a<A>(p.scale_log2, p.scale64);
     for (int k0 = 0; k0 < Nk; k0 += kGT) {
         __syncthreads();
         for (int i = tid; i < kGT * d; i += kGThreads) {
@@ -254,7 +208,7 @@ __global__ __launch_bounds__(kGThreads) void bwd_generic_dq(BwdParams p) {
         }
     }
     T* dQb = (T*)p.dQ + (int64_t)b * N * d;
-    const A sc = bscale<A>(p);
+    const A sc = scale_a<A>(p.scale, p.scale64);
 #pragma unroll
     for (int t = 0; t < kMaxPer; ++t) {
         const int i = tid + kGThreads * t, q = i % kGT, f = i / kGT;
@@ -295,7 +249,7 @@ __global__ __launch_bounds__(kGThreads) void bwd_generic_dkdv(BwdParams p) {
     for (int t = 0; t < kMaxPer; ++t) { accK[t] = (A)0; accV[t] = (A)0; }
     const A* nD = (const A*)p.nD + (int64_t)b * N;
     const A* nL = (const A*)p.nlse + (int64_t)b * N;
-    const A sl2 = bscale_log2<A>(p);
+    const A sl2 = scale_log2_a<A>(p.scale_log2, p.scale64);
     for (int q0 = 0; q0 < N; q0 += kGT) {
         __syncthreads();
         for (int i = tid; i < kGT * d; i += kGThreads) {
@@ -338,7 +292,7 @@ __global__ __launch_bounds__(kGThreads) void bwd_generic_dkdv(BwdParams p) {
     }
     T* dKb = (T*)p.dK + (int64_t)b * Nk * d;
     T* dVb = (T*)p.dV + (int64_t)b * Nk * dv;
-    const A sc = bscale<A>(p);
+    const A sc = scale_a<A>(p.scale, p.scale64);
 #pragma unroll
     for (int t = 0; t < kMaxPer; ++t) {
         const int i = tid + kGThreads * t, k = i % kGT, f = i / kGT;
@@ -542,15 +496,9 @@ static hipError_t launch_f32_mfma(const BwdParams& p, hipStream_t s) {
 // --------------------------------------------------------------------------
 // 2./3. MFMA fast path (bf16 / fp16; d, dv in {32, 64, 128}; N, Nk % 8 == 0;
 // 16-B aligned).  Token tiles of 64 are staged by LDS-DMA (buffer_load … lds)
-// into [rows][64 tokens] images with 128-B rows and a 16-B XOR swizzle
-// g(f) = ((f>>3)&3) | ((f>>1)&1)<<2 that makes BOTH access patterns
-// conflict-free: the transposed reads ds_read_b64_tr_b16 (A operands of the
-// score / dP products: 4 consecutive rows × 64 B per half-wave) and the
-// ds_read_b128 row reads (A operands of the gradient products: 16 rows per
-// lane group, one 16-B chunk each).
+// into the swizzled [rows][64 tokens] images of fa_bwd_common.h (img_chunk for the
+// writers here, ImgReader for the MFMA operands).
 // --------------------------------------------------------------------------
-__device__ __forceinline__ int swz16(int f) { return ((f >> 3) & 3) | (((f >> 1) & 1) << 2); }
-
 template <class T>
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t bslab(const void* base, int64_t off_elems, int64_t elems) {
     return __builtin_amdgcn_make_buffer_rsrc((void*)((const T*)base + off_elems), (short)0,
@@ -564,12 +512,11 @@ template <int R>
 __device__ __forceinline__ void dma_image(__amdgpu_buffer_rsrc_t rs, char* img, int ntok, int t0, int wave, int lane) {
 #pragma unroll
     for (int it = 0; it < R / 32; ++it) {
-        const int blk = it * 4 + wave;                 // 1-KiB block of the image
-        const int P = blk * 64 + lane;                 // 16-B chunk index (linear in LDS)
-        const int f = P >> 3, c = (P & 7) ^ swz16(f);  // logical chunk at that position
+        const int blk = it * 4 + wave;                    // 1-KiB block of the image
+        const ImgChunk ch = img_chunk(blk * 64 + lane);   // row and chunk of the 16 B this lane fills
         __builtin_amdgcn_raw_ptr_buffer_load_lds(
             rs, (__attribute__((address_space(3))) void*)(img + blk * 1024), 16,
-            (f * ntok + t0 + 8 * c) * 2, 0, 0, 0);
+            (ch.f * ntok + t0 + 8 * ch.c) * 2, 0, 0, 0);
     }
 }
 
@@ -582,12 +529,6 @@ __device__ __forceinline__ unsigned ld_agent(gu32* p) {
 __device__ __forceinline__ void st_agent(gu32* p, unsigned v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-
-// Per-lane constant parts of the two fragment reads of an image.
-struct FragAddr {
-    int tr[2][2];   // [token block tb][s & 1] byte offset of the transposed read (half2 = 0)
-    int row[2];     // [h-independent] b128 row read: swizzled chunk offsets need (r, chunk)
-};
 
 __device__ __forceinline__ int sig32(int r) { return (r & ~12) | ((r & 4) << 1) | ((r & 8) >> 1); }
 
@@ -629,7 +570,6 @@ __device__ void fused_combine(const BwdParams& p, int b, int qb) {
 template <class T, int D, int DV>
 __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
     typedef typename Frag8<T>::type F8;
-    typedef typename Frag8<T>::half F4;
     constexpr int KB = D * 128, VB = DV * 128, STAGE = KB + VB;
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
     // after bwd_fused: recompute dQ only on the slabs whose hand-off gave up, and make
@@ -666,27 +606,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
     const float cnl = c * p.nlse[(int64_t)b * N + qc];
     const float nDq = p.nD[(int64_t)b * N + qc];
 
-    // transposed-read lane offsets (see fa_fwd.hip): lane 4q+pp of 16-lane group g
-    const int g = lane >> 4, kh = g & 1, qq = (lane & 15) >> 2, pp = lane & 3;
-    const int sig = (pp == 1) ? 2 : (pp == 2) ? 1 : pp;
-    int tro[2][2];
-#pragma unroll
-    for (int tb = 0; tb < 2; ++tb)
-#pragma unroll
-        for (int sp = 0; sp < 2; ++sp) {
-            const int sw = ((sp << 1) | h) | (((qq >> 1) & 1) << 2);
-            tro[tb][sp] = (8 * h + qq) * 128 + (((tb * 4 + kh * 2 + (sig >> 1)) ^ sw) * 16) + (sig & 1) * 8;
-        }
-    const int rsw = swz16(r);
-    auto trfrag = [&](const char* img, int tb, int s) -> F8 {
-        const char* a = img + tro[tb][s & 1] + 16 * s * 128;
-        const F4 lo = __builtin_bit_cast(F4, ds_read_tr16(a));
-        const F4 hi = __builtin_bit_cast(F4, ds_read_tr16(a + 4 * 128));
-        return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    };
-    auto rowfrag = [&](const char* img, int cb, int tb, int s2) -> F8 {
-        return *(const F8*)(img + (cb * 32 + r) * 128 + (((tb * 4 + 2 * s2 + h) ^ rsw) * 16));
-    };
+    const ImgReader<T> rd(tid);
 
     f32x16 dq[D / 32];
 #pragma unroll
@@ -708,9 +628,9 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
 #pragma unroll
             for (int x = 0; x < 16; ++x) { sa[x] = 0.0f; dp[x] = 0.0f; }
 #pragma unroll
-            for (int s = 0; s < D / 16; ++s) sa = mfma32x32x16(trfrag(kimg, kb, s), qf[s], sa);
+            for (int s = 0; s < D / 16; ++s) sa = mfma32x32x16(rd.tr(kimg, kb, s), qf[s], sa);
 #pragma unroll
-            for (int s = 0; s < DV / 16; ++s) dp = mfma32x32x16(trfrag(vimg, kb, s), df[s], dp);
+            for (int s = 0; s < DV / 16; ++s) dp = mfma32x32x16(rd.tr(vimg, kb, s), df[s], dp);
             if (partial) {
 #pragma unroll
                 for (int x = 0; x < 16; ++x)
@@ -725,7 +645,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
 #pragma unroll
             for (int cb = 0; cb < D / 32; ++cb)
 #pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) dq[cb] = mfma32x32x16(rowfrag(kimg, cb, kb, s2), dsf[s2], dq[cb]);
+                for (int s2 = 0; s2 < 2; ++s2) dq[cb] = mfma32x32x16(rd.row(kimg, cb, kb, s2), dsf[s2], dq[cb]);
         }
     };
 
@@ -757,7 +677,6 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
 template <class T, int D, int DV>
 __global__ __launch_bounds__(256, 2) void bwd_dkdv_fast(BwdParams p) {
     typedef typename Frag8<T>::type F8;
-    typedef typename Frag8<T>::half F4;
     constexpr int QB = D * 128, OB = DV * 128, STAGE = QB + OB + 512;
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
     const int lid = xcd_remap(blockIdx.x, p.total_wg);
@@ -784,26 +703,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_fast(BwdParams p) {
     const float* nlse = p.nlse + (int64_t)b * N;
     const float* nDg = p.nD + (int64_t)b * N;
 
-    const int g = lane >> 4, kh = g & 1, qq = (lane & 15) >> 2, pp = lane & 3;
-    const int sig = (pp == 1) ? 2 : (pp == 2) ? 1 : pp;
-    int tro[2][2];
-#pragma unroll
-    for (int tb = 0; tb < 2; ++tb)
-#pragma unroll
-        for (int sp = 0; sp < 2; ++sp) {
-            const int sw = ((sp << 1) | h) | (((qq >> 1) & 1) << 2);
-            tro[tb][sp] = (8 * h + qq) * 128 + (((tb * 4 + kh * 2 + (sig >> 1)) ^ sw) * 16) + (sig & 1) * 8;
-        }
-    const int rsw = swz16(r);
-    auto trfrag = [&](const char* img, int tb, int s) -> F8 {
-        const char* a = img + tro[tb][s & 1] + 16 * s * 128;
-        const F4 lo = __builtin_bit_cast(F4, ds_read_tr16(a));
-        const F4 hi = __builtin_bit_cast(F4, ds_read_tr16(a + 4 * 128));
-        return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    };
-    auto rowfrag = [&](const char* img, int cb, int tb, int s2) -> F8 {
-        return *(const F8*)(img + (cb * 32 + r) * 128 + (((tb * 4 + 2 * s2 + h) ^ rsw) * 16));
-    };
+    const ImgReader<T> rd(tid);
 
     f32x16 dk[D / 32], dv[DV / 32];
 #pragma unroll
@@ -847,9 +747,9 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_fast(BwdParams p) {
                 dp[e] = d0[e]; dp[4 + e] = d1[e]; dp[8 + e] = d2[e]; dp[12 + e] = d3[e];
             }
 #pragma unroll
-            for (int s = 0; s < D / 16; ++s) sa = mfma32x32x16(trfrag(qimg, u, s), kf[s], sa);
+            for (int s = 0; s < D / 16; ++s) sa = mfma32x32x16(rd.tr(qimg, u, s), kf[s], sa);
 #pragma unroll
-            for (int s = 0; s < DV / 16; ++s) dp = mfma32x32x16(trfrag(oimg, u, s), vf[s], dp);
+            for (int s = 0; s < DV / 16; ++s) dp = mfma32x32x16(rd.tr(oimg, u, s), vf[s], dp);
             F8 pf[2], dsf[2];
 #pragma unroll
             for (int x = 0; x < 16; ++x) {
@@ -860,11 +760,11 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_fast(BwdParams p) {
 #pragma unroll
             for (int cb = 0; cb < DV / 32; ++cb)
 #pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) dv[cb] = mfma32x32x16(rowfrag(oimg, cb, u, s2), pf[s2], dv[cb]);
+                for (int s2 = 0; s2 < 2; ++s2) dv[cb] = mfma32x32x16(rd.row(oimg, cb, u, s2), pf[s2], dv[cb]);
 #pragma unroll
             for (int cb = 0; cb < D / 32; ++cb)
 #pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) dk[cb] = mfma32x32x16(rowfrag(qimg, cb, u, s2), dsf[s2], dk[cb]);
+                for (int s2 = 0; s2 < 2; ++s2) dk[cb] = mfma32x32x16(rd.row(qimg, cb, u, s2), dsf[s2], dk[cb]);
         }
     };
 
@@ -962,11 +862,10 @@ __device__ __forceinline__ void dma_image8(__amdgpu_buffer_rsrc_t rs, char* img,
     for (int it = 0; it < (NB + 7) / 8; ++it) {
         const int blk = it * 8 + wave;
         if (NB % 8 == 0 || blk < NB) {
-            const int P = blk * 64 + lane;
-            const int f = P >> 3, c = (P & 7) ^ swz16(f);
+            const ImgChunk ch = img_chunk(blk * 64 + lane);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(
                 rs, (__attribute__((address_space(3))) void*)(img + blk * 1024), 16,
-                (f * ntok + t0 + 8 * c) * 2, 0, 0, 0);
+                (ch.f * ntok + t0 + 8 * ch.c) * 2, 0, 0, 0);
         }
     }
 }
@@ -1087,9 +986,8 @@ __device__ __forceinline__ void dma_image8_asm(const u32x4& desc, char* img, int
     for (int it = 0; it < (NB + 7) / 8; ++it) {
         const int blk = it * 8 + wave;
         if (NB % 8 == 0 || blk < NB) {
-            const int P = blk * 64 + lane;
-            const int f = P >> 3, c = (P & 7) ^ swz16(f);
-            dma16_asm(desc, lds_addr(img + blk * 1024), (f * ntok + t0 + 8 * c) * 2);
+            const ImgChunk ch = img_chunk(blk * 64 + lane);
+            dma16_asm(desc, lds_addr(img + blk * 1024), (ch.f * ntok + t0 + 8 * ch.c) * 2);
         }
     }
 }
@@ -1220,8 +1118,12 @@ __global__ __launch_bounds__(512, 1) void bwd_fused(BwdParams p) {
         wait_count(h->cnt[ch] + t, (unsigned)pos, h->serr, h->err, h->garr, h->prog, KM, h->stall);
     };
 
+    // This lane's reads of the images.  The offsets of ImgReader (fa_bwd_common.h) are
+    // written out here, and the reads go through lambdas: built from the struct, this
+    // kernel's register allocation gains SGPR spills and, in two instantiations, 32 B of
+    // scratch; this form compiles to the code it had before the struct existed.
     const int g = lane >> 4, kh = g & 1, qq = (lane & 15) >> 2, pp = lane & 3;
-    const int sig = (pp == 1) ? 2 : (pp == 2) ? 1 : pp;
+    const int sig = tr_sig(pp);
     int tro[2][2];
 #pragma unroll
     for (int tb = 0; tb < 2; ++tb)
@@ -1231,15 +1133,8 @@ __global__ __launch_bounds__(512, 1) void bwd_fused(BwdParams p) {
             tro[tb][sp] = (8 * h + qq) * 128 + (((tb * 4 + kh * 2 + (sig >> 1)) ^ sw) * 16) + (sig & 1) * 8;
         }
     const int rsw = swz16(r);
-    auto trfrag = [&](const char* img, int tb, int s) -> F8 {
-        const char* a = img + tro[tb][s & 1] + 16 * s * 128;
-        const F4 lo = __builtin_bit_cast(F4, ds_read_tr16(a));
-        const F4 hi = __builtin_bit_cast(F4, ds_read_tr16(a + 4 * 128));
-        return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    };
-    auto rowfrag = [&](const char* img, int cb, int tb, int s2) -> F8 {
-        return *(const F8*)(img + (cb * 32 + r) * 128 + (((tb * 4 + 2 * s2 + h) ^ rsw) * 16));
-    };
+    auto trfrag = [&](const char* img, int tb, int s) -> F8 { return img_tr<T>(img, tro, tb, s); };
+    auto rowfrag = [&](const char* img, int cb, int tb, int s2) -> F8 { return img_row<T>(img, r, h, rsw, cb, tb, s2); };
     auto slice_of = [&](int i) {
         int t = (i - OFF * j) % NS;
         return t < 0 ? t + NS : t;
@@ -1526,10 +1421,8 @@ __global__ __launch_bounds__(512, 1) void bwd_fused(BwdParams p) {
             uint32_t ka[4];
             const int rswq = swz16(rq);
 #pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4)
-                ka[q4] = lds_addr(kimg + (cbq * 32 + rq) * 128 + ((((q4 >> 1) * 4 + 2 * (q4 & 1) + hq) ^ rswq) * 16));
-            const int qqq = (lq & 15) >> 2, ppq = lq & 3, khq = (lq >> 4) & 1;
-            const int sgq = (ppq == 1) ? 2 : (ppq == 2) ? 1 : ppq;
+            for (int q4 = 0; q4 < 4; ++q4) ka[q4] = lds_addr(kimg + img_row_off(rq, hq, rswq, cbq, q4 >> 1, q4 & 1));
+            const int qqq = (lq & 15) >> 2, khq = (lq >> 4) & 1, sgq = tr_sig(lq & 3);
             const uint32_t da = lds_addr(dsimg + (8 * hq + qqq) * 128 +
                                          (((uq * 4 + khq * 2 + (sgq >> 1)) ^ swzds(8 * hq + qqq)) * 16) + (sgq & 1) * 8);
             u32x4 fa[2];

@@ -21,7 +21,7 @@
 // Kernels:
 //  * circ_bwd_dq_tiled / circ_bwd_dkdv_tiled (bf16 / fp16, N % 8 == 0, 16-B aligned
 //    inputs): 4 waves x 32 queries (keys), 64-position tiles in the dense backward's
-//    swizzled [feature][64 tokens] LDS images (fa_bwd.hip) and its MFMA fragments;
+//    swizzled [feature][64 tokens] LDS images and MFMA fragments (fa_bwd_common.h);
 //    tiles are staged through registers (buffer loads return 0 past the slab, which
 //    zero-fills the features d..D−1 of a head dim inside a class) and double-buffered.
 //    A wave computes only the tiles that intersect its 32 bands and applies the
@@ -31,7 +31,7 @@
 //    double with the row statistics recomputed in double by the pre-pass.
 #include <type_traits>
 
-#include "fa_common.h"
+#include "fa_bwd_common.h"
 #include "fa_internal.h"
 #include "../../include/fa_hip.h"
 
@@ -52,16 +52,6 @@ struct CircBwdParams {
     double scale64;
 };
 
-__device__ __forceinline__ float cb_fma(float a, float b, float c) { return fmaf(a, b, c); }
-__device__ __forceinline__ double cb_fma(double a, double b, double c) { return fma(a, b, c); }
-__device__ __forceinline__ float cb_exp2(float x) { return exp2f(x); }
-__device__ __forceinline__ double cb_exp2(double x) { return exp2(x); }
-template <class A> __device__ __forceinline__ A cb_scale(const CircBwdParams& p) {
-    if constexpr (sizeof(A) == 8) return p.scale64; else return p.scale;
-}
-template <class A> __device__ __forceinline__ A cb_scale_log2(const CircBwdParams& p) {
-    if constexpr (sizeof(A) == 8) return p.scale64 * 1.4426950408889634074; else return p.scale_log2;
-}
 // (x mod N) in [0, N) for any sign of x
 __device__ __forceinline__ int cb_mod(int64_t x, int N) {
     const int64_t r = x % N;
@@ -83,7 +73,7 @@ __global__ __launch_bounds__(256) void circ_bwd_prepass(CircBwdParams p) {
     const T* O = (const T*)p.O + b * (int64_t)N * p.dv + n;
     const T* dO = (const T*)p.dO + b * (int64_t)N * p.dv + n;
     A acc = (A)0;
-    for (int c = 0; c < p.dv; ++c) acc = cb_fma((A)dO[(int64_t)c * N], (A)O[(int64_t)c * N], acc);
+    for (int c = 0; c < p.dv; ++c) acc = fma_a((A)dO[(int64_t)c * N], (A)O[(int64_t)c * N], acc);
     ((A*)p.nD)[idx] = -acc;
     if constexpr (sizeof(A) == 8) {
         const T* Q = (const T*)p.Q + b * (int64_t)N * p.d + n;
@@ -105,49 +95,12 @@ __global__ __launch_bounds__(256) void circ_bwd_prepass(CircBwdParams p) {
     }
 }
 
-// 16-B variant (bf16 / fp16, N % 8 == 0, O and dO 16-B aligned): a thread owns 8
-// consecutive queries and keeps 16 row loads in flight (cf. bwd_prepass_v, fa_bwd.hip).
+// 16-B variant (bf16 / fp16, N % 8 == 0, O and dO 16-B aligned): 8 queries per thread.
 template <class T>
 __global__ __launch_bounds__(256) void circ_bwd_prepass_v(CircBwdParams p) {
-    constexpr int U = 8;
     const int64_t g8 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int N = p.N;
-    if (g8 >= (int64_t)N * p.batch / 8) return;
-    const int64_t idx = g8 * 8, b = idx / N, n = idx - b * N;
-    const T* O = (const T*)p.O + b * (int64_t)N * p.dv + n;
-    const T* dO = (const T*)p.dO + b * (int64_t)N * p.dv + n;
-    float acc[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) acc[k] = 0.0f;
-    auto fma8 = [&](const u32x4& a, const u32x4& c) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const unsigned wa = a[k], wc = c[k];
-            acc[2 * k] = fmaf((float)__builtin_bit_cast(T, (unsigned short)(wa & 0xFFFFu)),
-                              (float)__builtin_bit_cast(T, (unsigned short)(wc & 0xFFFFu)), acc[2 * k]);
-            acc[2 * k + 1] = fmaf((float)__builtin_bit_cast(T, (unsigned short)(wa >> 16)),
-                                  (float)__builtin_bit_cast(T, (unsigned short)(wc >> 16)), acc[2 * k + 1]);
-        }
-    };
-    int c = 0;
-    for (; c + U <= p.dv; c += U) {
-        u32x4 ro[U], rd[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            ro[u] = *(const u32x4*)(O + (int64_t)(c + u) * N);
-            rd[u] = *(const u32x4*)(dO + (int64_t)(c + u) * N);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) fma8(rd[u], ro[u]);
-    }
-    for (; c < p.dv; ++c) fma8(*(const u32x4*)(dO + (int64_t)c * N), *(const u32x4*)(O + (int64_t)c * N));
-    float* nD = (float*)p.nD;
-    float* nlse = (float*)p.nlse;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        nD[idx + k] = -acc[k];
-        nlse[idx + k] = -(p.m[idx + k] + logf(p.l[idx + k])) / p.scale;
-    }
+    if (g8 >= (int64_t)p.N * p.batch / 8) return;
+    prepass_rows8((const T*)p.O, (const T*)p.dO, p.l, p.m, (float*)p.nD, (float*)p.nlse, g8 * 8, p.N, p.dv, p.scale);
 }
 
 // W = 1: the softmax over a single band entry is exactly 1, so dS = P (dP − D) = 0:
@@ -208,7 +161,7 @@ __global__ __launch_bounds__(kCThreads) void circ_bwd_dq_simt(CircBwdParams p) {
     for (int t = 0; t < kMaxPer; ++t) acc[t] = (A)0;
     const A* nD = (const A*)p.nD + (int64_t)b * N;
     const A* nL = (const A*)p.nlse + (int64_t)b * N;
-    const A sl2 = cb_scale_log2<A>(p);
+    const A sl2 = scale_log2_a<A>(p.scale_log2, p.scale64);
     const int base = cb_mod((int64_t)q0 - p.p, N);
     const int64_t U = (int64_t)kCT + W - 1;
     for (int64_t u0 = 0; u0 < U; u0 += kCT) {
@@ -229,9 +182,9 @@ __global__ __launch_bounds__(kCThreads) void circ_bwd_dq_simt(CircBwdParams p) {
             A ds = (A)0;
             if (q0 + q < N && t >= 0 && t < W) {
                 A s = (A)0, dp = (A)0;
-                for (int f = 0; f < d; ++f) s = cb_fma(sQ[q * ld + f], sK[k * ld + f], s);
-                for (int f = 0; f < dv; ++f) dp = cb_fma(sdO[q * ldv + f], sV[k * ldv + f], dp);
-                const A pr = cb_exp2((s + nL[q0 + q]) * sl2);
+                for (int f = 0; f < d; ++f) s = fma_a(sQ[q * ld + f], sK[k * ld + f], s);
+                for (int f = 0; f < dv; ++f) dp = fma_a(sdO[q * ldv + f], sV[k * ldv + f], dp);
+                const A pr = exp2_a((s + nL[q0 + q]) * sl2);
                 ds = pr * (dp + nD[q0 + q]);
             }
             sdS[q * (kCT + 1) + k] = ds;
@@ -242,13 +195,13 @@ __global__ __launch_bounds__(kCThreads) void circ_bwd_dq_simt(CircBwdParams p) {
             const int i = tid + kCThreads * t, q = i % kCT, f = i / kCT;
             if (f < d) {
                 A a = acc[t];
-                for (int k = 0; k < kCT; ++k) a = cb_fma(sdS[q * (kCT + 1) + k], sK[k * ld + f], a);
+                for (int k = 0; k < kCT; ++k) a = fma_a(sdS[q * (kCT + 1) + k], sK[k * ld + f], a);
                 acc[t] = a;
             }
         }
     }
     T* dQb = (T*)p.dQ + (int64_t)b * N * d;
-    const A sc = cb_scale<A>(p);
+    const A sc = scale_a<A>(p.scale, p.scale64);
 #pragma unroll
     for (int t = 0; t < kMaxPer; ++t) {
         const int i = tid + kCThreads * t, q = i % kCT, f = i / kCT;
@@ -292,7 +245,7 @@ __global__ __launch_bounds__(kCThreads) void circ_bwd_dkdv_simt(CircBwdParams p)
     for (int t = 0; t < kMaxPer; ++t) { accK[t] = (A)0; accV[t] = (A)0; }
     const A* nD = (const A*)p.nD + (int64_t)b * N;
     const A* nL = (const A*)p.nlse + (int64_t)b * N;
-    const A sl2 = cb_scale_log2<A>(p);
+    const A sl2 = scale_log2_a<A>(p.scale_log2, p.scale64);
     const int base = cb_mod((int64_t)k0 + p.p - W + 1, N);
     const int64_t U = (int64_t)kCT + W - 1;
     for (int64_t u0 = 0; u0 < U; u0 += kCT) {
@@ -315,9 +268,9 @@ __global__ __launch_bounds__(kCThreads) void circ_bwd_dkdv_simt(CircBwdParams p)
             A pr = (A)0, ds = (A)0;
             if (k0 + k < N && t >= 0 && t < W) {
                 A s = (A)0, dp = (A)0;
-                for (int f = 0; f < d; ++f) s = cb_fma(sQ[q * ld + f], sK[k * ld + f], s);
-                for (int f = 0; f < dv; ++f) dp = cb_fma(sdO[q * ldv + f], sV[k * ldv + f], dp);
-                pr = cb_exp2((s + sRow[q]) * sl2);
+                for (int f = 0; f < d; ++f) s = fma_a(sQ[q * ld + f], sK[k * ld + f], s);
+                for (int f = 0; f < dv; ++f) dp = fma_a(sdO[q * ldv + f], sV[k * ldv + f], dp);
+                pr = exp2_a((s + sRow[q]) * sl2);
                 ds = pr * (dp + sRow[kCT + q]);
             }
             sP[q * (kCT + 1) + k] = pr;
@@ -329,19 +282,19 @@ __global__ __launch_bounds__(kCThreads) void circ_bwd_dkdv_simt(CircBwdParams p)
             const int i = tid + kCThreads * t, k = i % kCT, f = i / kCT;
             if (f < d) {
                 A a = accK[t];
-                for (int q = 0; q < kCT; ++q) a = cb_fma(sdS[q * (kCT + 1) + k], sQ[q * ld + f], a);
+                for (int q = 0; q < kCT; ++q) a = fma_a(sdS[q * (kCT + 1) + k], sQ[q * ld + f], a);
                 accK[t] = a;
             }
             if (f < dv) {
                 A a = accV[t];
-                for (int q = 0; q < kCT; ++q) a = cb_fma(sP[q * (kCT + 1) + k], sdO[q * ldv + f], a);
+                for (int q = 0; q < kCT; ++q) a = fma_a(sP[q * (kCT + 1) + k], sdO[q * ldv + f], a);
                 accV[t] = a;
             }
         }
     }
     T* dKb = (T*)p.dK + (int64_t)b * N * d;
     T* dVb = (T*)p.dV + (int64_t)b * N * dv;
-    const A sc = cb_scale<A>(p);
+    const A sc = scale_a<A>(p.scale, p.scale64);
 #pragma unroll
     for (int t = 0; t < kMaxPer; ++t) {
         const int i = tid + kCThreads * t, k = i % kCT, f = i / kCT;
@@ -353,15 +306,11 @@ __global__ __launch_bounds__(kCThreads) void circ_bwd_dkdv_simt(CircBwdParams p)
 }
 
 // --------------------------------------------------------------------------
-// 2./3. MFMA path.  LDS images and fragments are the dense backward's (fa_bwd.hip):
-// [rows][64 tokens] with 128-B rows and the 16-B XOR swizzle swz16, which keeps both
-// the transposed reads (A operands of S / dP) and the b128 row reads (A operands of
-// the gradient products) conflict-free.  Here a tile's 8-token chunks are loaded to
-// registers (a chunk never straddles N: the union start is rounded down to 8 and
-// N % 8 == 0) and written to LDS one iteration later.
+// 2./3. MFMA path.  LDS images and fragments are the dense backward's, the swizzled
+// [rows][64 tokens] image of fa_bwd_common.h (img_chunk, ImgReader).  Here a tile's
+// 8-token chunks are loaded to registers (a chunk never straddles N: the union start
+// is rounded down to 8 and N % 8 == 0) and written to LDS one iteration later.
 // --------------------------------------------------------------------------
-__device__ __forceinline__ int cb_swz16(int f) { return ((f >> 3) & 3) | (((f >> 1) & 1) << 2); }
-
 constexpr int kOobOffset = 0x7FFFFFF0;   // past every slab (extent < INT32_MAX): reads 0
 
 // Registers <- the [R rows][64 tokens] tile whose first token is tok0 (< N, % 8 == 0)
@@ -371,10 +320,9 @@ __device__ __forceinline__ void cb_gload(u32x4 (&reg)[R / 32], __amdgpu_buffer_r
                                          int tok0, int tid) {
 #pragma unroll
     for (int it = 0; it < R / 32; ++it) {
-        const int P = it * 256 + tid;
-        const int f = P >> 3, c = (P & 7) ^ cb_swz16(f);
-        const int tok = (tok0 + 8 * c) % N;
-        reg[it] = __builtin_amdgcn_raw_buffer_load_b128(rs, f < rows ? (f * N + tok) * (int)sizeof(T) : kOobOffset, 0, 0);
+        const ImgChunk ch = img_chunk(it * 256 + tid);
+        const int tok = (tok0 + 8 * ch.c) % N;
+        reg[it] = __builtin_amdgcn_raw_buffer_load_b128(rs, ch.f < rows ? (ch.f * N + tok) * (int)sizeof(T) : kOobOffset, 0, 0);
     }
 }
 template <int R>
@@ -415,7 +363,6 @@ __device__ __forceinline__ CbUnion cb_union(int s0, int W) {
 template <class T, int D, int DV>
 __global__ __launch_bounds__(256, (D + DV > 192) ? 1 : 2) void circ_bwd_dq_tiled(CircBwdParams p) {
     typedef typename Frag8<T>::type F8;
-    typedef typename Frag8<T>::half F4;
     constexpr int KB = D * 128, VB = DV * 128, STAGE = KB + VB;
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
     const int lid = xcd_remap(blockIdx.x, p.total_wg);
@@ -441,27 +388,7 @@ __global__ __launch_bounds__(256, (D + DV > 192) ? 1 : 2) void circ_bwd_dq_tiled
     const float cnl = c * ((const float*)p.nlse)[(int64_t)b * N + qc];
     const float nDq = ((const float*)p.nD)[(int64_t)b * N + qc];
 
-    // transposed-read lane offsets (see fa_bwd.hip): lane 4q+pp of 16-lane group g
-    const int g = lane >> 4, kh = g & 1, qq = (lane & 15) >> 2, pp = lane & 3;
-    const int sig = (pp == 1) ? 2 : (pp == 2) ? 1 : pp;
-    int tro[2][2];
-#pragma unroll
-    for (int tb = 0; tb < 2; ++tb)
-#pragma unroll
-        for (int sp = 0; sp < 2; ++sp) {
-            const int sw = ((sp << 1) | h) | (((qq >> 1) & 1) << 2);
-            tro[tb][sp] = (8 * h + qq) * 128 + (((tb * 4 + kh * 2 + (sig >> 1)) ^ sw) * 16) + (sig & 1) * 8;
-        }
-    const int rsw = cb_swz16(r);
-    auto trfrag = [&](const char* img, int tb, int s) -> F8 {
-        const char* a = img + tro[tb][s & 1] + 16 * s * 128;
-        const F4 lo = __builtin_bit_cast(F4, ds_read_tr16(a));
-        const F4 hi = __builtin_bit_cast(F4, ds_read_tr16(a + 4 * 128));
-        return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    };
-    auto rowfrag = [&](const char* img, int cb, int tb, int s2) -> F8 {
-        return *(const F8*)(img + (cb * 32 + r) * 128 + (((tb * 4 + 2 * s2 + h) ^ rsw) * 16));
-    };
+    const ImgReader<T> rd(tid);
 
     f32x16 dq[D / 32];
 #pragma unroll
@@ -491,9 +418,9 @@ __global__ __launch_bounds__(256, (D + DV > 192) ? 1 : 2) void circ_bwd_dq_tiled
 #pragma unroll
             for (int x = 0; x < 16; ++x) { sa[x] = 0.0f; dp[x] = 0.0f; }
 #pragma unroll
-            for (int s = 0; s < D / 16; ++s) sa = mfma32x32x16(trfrag(kimg, kb, s), qf[s], sa);
+            for (int s = 0; s < D / 16; ++s) sa = mfma32x32x16(rd.tr(kimg, kb, s), qf[s], sa);
 #pragma unroll
-            for (int s = 0; s < DV / 16; ++s) dp = mfma32x32x16(trfrag(vimg, kb, s), df[s], dp);
+            for (int s = 0; s < DV / 16; ++s) dp = mfma32x32x16(rd.tr(vimg, kb, s), df[s], dp);
             float pr[16];
 #pragma unroll
             for (int x = 0; x < 16; ++x) pr[x] = exp2_fast(fmaf(sa[x], c, cnl));
@@ -510,7 +437,7 @@ __global__ __launch_bounds__(256, (D + DV > 192) ? 1 : 2) void circ_bwd_dq_tiled
 #pragma unroll
             for (int cb = 0; cb < D / 32; ++cb)
 #pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) dq[cb] = mfma32x32x16(rowfrag(kimg, cb, kb, s2), dsf[s2], dq[cb]);
+                for (int s2 = 0; s2 < 2; ++s2) dq[cb] = mfma32x32x16(rd.row(kimg, cb, kb, s2), dsf[s2], dq[cb]);
         }
     };
 
@@ -552,7 +479,6 @@ __global__ __launch_bounds__(256, (D + DV > 192) ? 1 : 2) void circ_bwd_dq_tiled
 template <class T, int D, int DV>
 __global__ __launch_bounds__(256, (D + DV > 128) ? 1 : 2) void circ_bwd_dkdv_tiled(CircBwdParams p) {
     typedef typename Frag8<T>::type F8;
-    typedef typename Frag8<T>::half F4;
     constexpr int QB = D * 128, OB = DV * 128, STAGE = QB + OB + 512;
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
     const int lid = xcd_remap(blockIdx.x, p.total_wg);
@@ -577,26 +503,7 @@ __global__ __launch_bounds__(256, (D + DV > 128) ? 1 : 2) void circ_bwd_dkdv_til
     const float* nlse = (const float*)p.nlse + (int64_t)b * N;
     const float* nDg = (const float*)p.nD + (int64_t)b * N;
 
-    const int g = lane >> 4, kh = g & 1, qq = (lane & 15) >> 2, pp = lane & 3;
-    const int sig = (pp == 1) ? 2 : (pp == 2) ? 1 : pp;
-    int tro[2][2];
-#pragma unroll
-    for (int tb = 0; tb < 2; ++tb)
-#pragma unroll
-        for (int sp = 0; sp < 2; ++sp) {
-            const int sw = ((sp << 1) | h) | (((qq >> 1) & 1) << 2);
-            tro[tb][sp] = (8 * h + qq) * 128 + (((tb * 4 + kh * 2 + (sig >> 1)) ^ sw) * 16) + (sig & 1) * 8;
-        }
-    const int rsw = cb_swz16(r);
-    auto trfrag = [&](const char* img, int tb, int s) -> F8 {
-        const char* a = img + tro[tb][s & 1] + 16 * s * 128;
-        const F4 lo = __builtin_bit_cast(F4, ds_read_tr16(a));
-        const F4 hi = __builtin_bit_cast(F4, ds_read_tr16(a + 4 * 128));
-        return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    };
-    auto rowfrag = [&](const char* img, int cb, int tb, int s2) -> F8 {
-        return *(const F8*)(img + (cb * 32 + r) * 128 + (((tb * 4 + 2 * s2 + h) ^ rsw) * 16));
-    };
+    const ImgReader<T> rd(tid);
 
     f32x16 dk[D / 32], dvv[DV / 32];
 #pragma unroll
@@ -644,9 +551,9 @@ __global__ __launch_bounds__(256, (D + DV > 128) ? 1 : 2) void circ_bwd_dkdv_til
                 dp[e] = d0[e]; dp[4 + e] = d1[e]; dp[8 + e] = d2[e]; dp[12 + e] = d3[e];
             }
 #pragma unroll
-            for (int s = 0; s < D / 16; ++s) sa = mfma32x32x16(trfrag(qimg, u, s), kf[s], sa);
+            for (int s = 0; s < D / 16; ++s) sa = mfma32x32x16(rd.tr(qimg, u, s), kf[s], sa);
 #pragma unroll
-            for (int s = 0; s < DV / 16; ++s) dp = mfma32x32x16(trfrag(oimg, u, s), vf[s], dp);
+            for (int s = 0; s < DV / 16; ++s) dp = mfma32x32x16(rd.tr(oimg, u, s), vf[s], dp);
             float pr[16];
 #pragma unroll
             for (int x = 0; x < 16; ++x) pr[x] = exp2_fast(sa[x] * c);
@@ -666,11 +573,11 @@ __global__ __launch_bounds__(256, (D + DV > 128) ? 1 : 2) void circ_bwd_dkdv_til
 #pragma unroll
             for (int cb = 0; cb < DV / 32; ++cb)
 #pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) dvv[cb] = mfma32x32x16(rowfrag(oimg, cb, u, s2), pf[s2], dvv[cb]);
+                for (int s2 = 0; s2 < 2; ++s2) dvv[cb] = mfma32x32x16(rd.row(oimg, cb, u, s2), pf[s2], dvv[cb]);
 #pragma unroll
             for (int cb = 0; cb < D / 32; ++cb)
 #pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) dk[cb] = mfma32x32x16(rowfrag(qimg, cb, u, s2), dsf[s2], dk[cb]);
+                for (int s2 = 0; s2 < 2; ++s2) dk[cb] = mfma32x32x16(rd.row(qimg, cb, u, s2), dsf[s2], dk[cb]);
         }
     };
 

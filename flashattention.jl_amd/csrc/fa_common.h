@@ -108,4 +108,17 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t slab_rsrc(const T* base, uint3
 
 template <class T> __device__ __forceinline__ T zero_val() { return (T)0.0f; }
 
+// SIMT paths templated on the accumulation type A (float, or double for Float64):
+// fma / 2^x of that type, and τ / τ·log2 e picked from a float and a double τ.
+__device__ __forceinline__ float fma_a(float a, float b, float c) { return fmaf(a, b, c); }
+__device__ __forceinline__ double fma_a(double a, double b, double c) { return fma(a, b, c); }
+__device__ __forceinline__ float exp2_a(float x) { return exp2f(x); }
+__device__ __forceinline__ double exp2_a(double x) { return exp2(x); }
+template <class A> __device__ __forceinline__ A scale_a(float scale, double scale64) {
+    if constexpr (sizeof(A) == 8) return scale64; else return scale;
+}
+template <class A> __device__ __forceinline__ A scale_log2_a(float scale_log2, double scale64) {
+    if constexpr (sizeof(A) == 8) return scale64 * 1.4426950408889634074; else return scale_log2;
+}
+
 }  // namespace fa
