@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <string>
 
@@ -315,6 +316,101 @@ int fa_dense_bwd(int dtype, const void* Q, const void* K, const void* V, const v
     a.scale64 = resolve_scale64(scale, d);
     const char* why = "";
     const int rc = fa::launch_dense_bwd(a, (hipStream_t)hip_stream, &why);
+    return rc == FA_OK ? ok() : fail(rc, fn, why);
+}
+
+// Not part of the public header: launch order of the causal fast forward's query blocks
+// 0 in order; 1 slab by slab, a slab's heaviest (last) block first; 2 block-major inside each
+// XCD's share of the grid, heaviest blocks of all its slabs first (where that share holds
+// whole slabs, else as 1): the default.  Benchmark knob; returns the previous value (-2 for an invalid
+// argument).
+int fa_debug_set_causal_order(int v) {
+    const int old = fa::g_causal_rev;
+    if (v < 0 || v > 2) return -2;
+    fa::g_causal_rev = v;
+    return old;
+}
+
+// The checks fa_causal_fwd / fa_causal_bwd share after the null-pointer and DimensionMismatch
+// ones, in order: head dims and Nk >= N, then the kernels' 32-bit extents (the launchers'
+// own conditions, repeated here so that they precede the workspace check and any launch).
+static int causal_shape_check(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch,
+                              bool bwd, const char** why) {
+    if (d > fa::kMaxHeadDim || dv > fa::kMaxHeadDim) {
+        *why = "head dimension exceeds the compiled maximum (128)";
+        return FA_ERR_UNSUPPORTED;
+    }
+    if (Nk < N) {
+        *why = "causal attention needs Nk >= N (a query would see no key)";
+        return FA_ERR_UNSUPPORTED;
+    }
+    const bool big = N > INT32_MAX / 2 || Nk > INT32_MAX / 2 || N * d > INT32_MAX || Nk * d > INT32_MAX ||
+                     Nk * dv > INT32_MAX || N * dv > INT32_MAX ||
+                     (bwd && (N * batch > INT32_MAX / 2 || Nk * batch > INT32_MAX / 2)) ||
+                     (dtype == FA_DTYPE_F64 && (N + 63) / 64 * batch > INT32_MAX);
+    if (big) {
+        *why = "extent exceeds the kernels' 32-bit addressing";
+        return FA_ERR_UNSUPPORTED;
+    }
+    return FA_OK;
+}
+
+size_t fa_causal_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
+    if (!valid_dtype(dtype) || N < 1 || Nk < N || d < 1 || dv < 1 || batch < 1) return 0;
+    return fa::causal_fwd_workspace(dtype, N, Nk, d, dv, batch);
+}
+
+int fa_causal_fwd(int dtype, const void* Q, const void* K, const void* V, void* O, float* l, float* m,
+                  int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, float scale,
+                  void* workspace, size_t workspace_bytes, void* hip_stream) {
+    static const char* fn = "fa_causal_fwd";
+    if (!valid_dtype(dtype)) return fail(FA_ERR_INVALID_ARG, fn, "unknown dtype");
+    if (N < 0 || Nk < 0 || d < 1 || dv < 1 || batch < 0)
+        return fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: N, Nk, batch must be >= 0 and d, dv >= 1");
+    if (N == 0 || batch == 0) return ok();   // no query: nothing to write
+    if (!Q || !K || !V || !O || !l || !m) return fail(FA_ERR_INVALID_ARG, fn, "null pointer");
+    const char* why = "";
+    int rc = causal_shape_check(dtype, N, Nk, d, dv, batch, false, &why);
+    if (rc != FA_OK) return fail(rc, fn, why);
+    const size_t need = fa::causal_fwd_workspace(dtype, N, Nk, d, dv, batch);
+    if (need > 0 && (!workspace || workspace_bytes < need))
+        return fail(FA_ERR_WORKSPACE, fn, "workspace missing or smaller than fa_causal_fwd_workspace()");
+    fa::DenseArgs a{dtype, Q, K, V, O, l, m, N, Nk, d, dv, batch, resolve_scale(scale, d)};
+    a.scale64 = resolve_scale64(scale, d);
+    a.workspace = workspace;
+    a.workspace_bytes = workspace_bytes;
+    a.causal = 1;
+    rc = fa::launch_dense_fwd(a, (hipStream_t)hip_stream, &why);
+    return rc == FA_OK ? ok() : fail(rc, fn, why);
+}
+
+size_t fa_causal_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
+    if (!valid_dtype(dtype) || N < 1 || Nk < N || d < 1 || dv < 1 || batch < 1) return 0;
+    return fa::causal_bwd_workspace(dtype, N, Nk, d, dv, batch);
+}
+
+int fa_causal_bwd(int dtype, const void* Q, const void* K, const void* V, const void* O, const void* dO,
+                  const float* l, const float* m, void* dQ, void* dK, void* dV, int64_t N, int64_t Nk,
+                  int64_t d, int64_t dv, int64_t batch, float scale, void* workspace,
+                  size_t workspace_bytes, void* hip_stream) {
+    static const char* fn = "fa_causal_bwd";
+    if (!valid_dtype(dtype)) return fail(FA_ERR_INVALID_ARG, fn, "unknown dtype");
+    if (N < 0 || Nk < 0 || d < 1 || dv < 1 || batch < 0)
+        return fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: N, Nk, batch must be >= 0 and d, dv >= 1");
+    if (N == 0 || batch == 0) return ok();   // no query (and, with Nk >= N required, no call with keys only)
+    if (!Q || !K || !V || !O || !dO || !l || !m || !dQ || !dK || !dV)
+        return fail(FA_ERR_INVALID_ARG, fn, "null pointer");
+    const char* why = "";
+    int rc = causal_shape_check(dtype, N, Nk, d, dv, batch, true, &why);
+    if (rc != FA_OK) return fail(rc, fn, why);
+    const size_t need = fa::causal_bwd_workspace(dtype, N, Nk, d, dv, batch);
+    if (!workspace || workspace_bytes < need)
+        return fail(FA_ERR_WORKSPACE, fn, "workspace missing or smaller than fa_causal_bwd_workspace()");
+    fa::DenseBwdArgs a{dtype, Q, K, V, O, dO, l, m, dQ, dK, dV, N, Nk, d, dv, batch,
+                       resolve_scale(scale, d), workspace, workspace_bytes};
+    a.scale64 = resolve_scale64(scale, d);
+    a.causal = 1;
+    rc = fa::launch_dense_bwd(a, (hipStream_t)hip_stream, &why);
     return rc == FA_OK ? ok() : fail(rc, fn, why);
 }
 

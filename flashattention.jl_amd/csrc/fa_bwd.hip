@@ -85,6 +85,10 @@ struct BwdParams {
     const unsigned* sguard = nullptr;          // ... and then only on the slabs b with sguard[b] != 0
     const unsigned* cguard = nullptr;          // bwd_dq_fast: combine the wrapped slices bwd_fused left (*cguard != 0)
     const unsigned* fin = nullptr;             // ... those with fin[b][t] == 2
+    // causal (fa_causal_bwd; read by the CAUSAL instantiations only): query i sees keys
+    // j <= i + off, off = Nk - N of the caller's extents (the padded path rounds N and Nk up
+    // separately and keeps this off)
+    int causal = 0, off = 0;
 };
 
 constexpr unsigned kBwdHdrMagic = 0x46414200u;   // "FAB\0"
@@ -140,7 +144,7 @@ constexpr int kGT = 32;          // tile edge
 constexpr int kGThreads = 256;
 
 // dQ: one block per (b, 32-query tile).
-template <class T, class A>
+template <class T, class A, bool CAUSAL = false>
 __global__ __launch_bounds__(kGThreads) void bwd_generic_dq(BwdParams p) {
     extern __shared__ __attribute__((aligned(16))) char gsm_raw[];
     A* const gsm = (A*)gsm_raw;
@@ -173,7 +177,9 @@ __global__ __launch_bounds__(kGThreads) void bwd_generic_dq(BwdParams p) {
     const A* nD = (const A*)p.nD + (int64_t)b * N;
     const A* nL = (const A*)p.nlse + (int64_t)b * N;
     const A sl2 = scale_log2_a<A>(p.scale_log2, p.scale64);
-    for (int k0 = 0; k0 < Nk; k0 += kGT) {
+    int kend = Nk;   // causal: keys up to the tile's last real query's limit
+    if constexpr (CAUSAL) kend = min(Nk, min(q0 + kGT - 1, N - 1) + p.off + 1);
+    for (int k0 = 0; k0 < kend; k0 += kGT) {
         __syncthreads();
         for (int i = tid; i < kGT * d; i += kGThreads) {
             const int k = i % kGT, f = i / kGT;
@@ -187,7 +193,9 @@ __global__ __launch_bounds__(kGThreads) void bwd_generic_dq(BwdParams p) {
         for (int e = tid; e < kGT * kGT; e += kGThreads) {
             const int q = e / kGT, k = e % kGT;
             A ds = (A)0;
-            if (q0 + q < N && k0 + k < Nk) {
+            bool vis = q0 + q < N && k0 + k < Nk;
+            if constexpr (CAUSAL) vis = vis && k0 + k <= q0 + q + p.off;
+            if (vis) {
                 A s = (A)0, dp = (A)0;
                 for (int f = 0; f < d; ++f) s = fma_a(sQ[q * ld + f], sK[k * ld + f], s);
                 for (int f = 0; f < dv; ++f) dp = fma_a(sdO[q * ldv + f], sV[k * ldv + f], dp);
@@ -217,7 +225,7 @@ __global__ __launch_bounds__(kGThreads) void bwd_generic_dq(BwdParams p) {
 }
 
 // dK, dV: one block per (b, 32-key tile).
-template <class T, class A>
+template <class T, class A, bool CAUSAL = false>
 __global__ __launch_bounds__(kGThreads) void bwd_generic_dkdv(BwdParams p) {
     extern __shared__ __attribute__((aligned(16))) char gsm_raw[];
     A* const gsm = (A*)gsm_raw;
@@ -250,7 +258,9 @@ __global__ __launch_bounds__(kGThreads) void bwd_generic_dkdv(BwdParams p) {
     const A* nD = (const A*)p.nD + (int64_t)b * N;
     const A* nL = (const A*)p.nlse + (int64_t)b * N;
     const A sl2 = scale_log2_a<A>(p.scale_log2, p.scale64);
-    for (int q0 = 0; q0 < N; q0 += kGT) {
+    int qbeg = 0;   // causal: the first query tile that sees the block's first key
+    if constexpr (CAUSAL) qbeg = max(0, k0 - p.off) / kGT * kGT;
+    for (int q0 = qbeg; q0 < N; q0 += kGT) {
         __syncthreads();
         for (int i = tid; i < kGT * d; i += kGThreads) {
             const int q = i % kGT, f = i / kGT;
@@ -264,7 +274,9 @@ __global__ __launch_bounds__(kGThreads) void bwd_generic_dkdv(BwdParams p) {
         for (int e = tid; e < kGT * kGT; e += kGThreads) {
             const int q = e / kGT, k = e % kGT;
             A pr = (A)0, ds = (A)0;
-            if (q0 + q < N && k0 + k < Nk) {
+            bool vis = q0 + q < N && k0 + k < Nk;
+            if constexpr (CAUSAL) vis = vis && k0 + k <= q0 + q + p.off;
+            if (vis) {
                 A s = (A)0, dp = (A)0;
                 for (int f = 0; f < d; ++f) s = fma_a(sQ[q * ld + f], sK[k * ld + f], s);
                 for (int f = 0; f < dv; ++f) dp = fma_a(sdO[q * ldv + f], sV[k * ldv + f], dp);
@@ -321,7 +333,7 @@ __global__ __launch_bounds__(kGThreads) void bwd_generic_dkdv(BwdParams p) {
 constexpr int kF32T = 32;   // tile of the streamed side
 constexpr int kF32R = 33;   // LDS row (floats)
 
-template <int D, int DV>
+template <int D, int DV, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void bwd_dkdv_f32(BwdParams p) {
     __shared__ float sQ[D * kF32R], sdO[DV * kF32R], sL[kF32T], sD[kF32T];
     const int N = p.N, Nk = p.Nk, d = p.d, dv = p.dv;
@@ -350,7 +362,9 @@ __global__ __launch_bounds__(256) void bwd_dkdv_f32(BwdParams p) {
     const float c = p.scale_log2;
     const float* nD = p.nD + (int64_t)b * N;
     const float* nL = p.nlse + (int64_t)b * N;
-    for (int q0 = 0; q0 < N; q0 += kF32T) {
+    int qbeg = 0;   // causal: the first query tile that sees the block's first key
+    if constexpr (CAUSAL) qbeg = max(0, k0 - p.off) / kF32T * kF32T;
+    for (int q0 = qbeg; q0 < N; q0 += kF32T) {
         __syncthreads();
         for (int i = tid; i < D * kF32T; i += 256) {
             const int q = i % kF32T, f = i / kF32T;
@@ -376,6 +390,9 @@ __global__ __launch_bounds__(256) void bwd_dkdv_f32(BwdParams p) {
 #pragma unroll
         for (int x = 0; x < 16; ++x) {
             const int q = acc_row(x, h);
+            if constexpr (CAUSAL) {              // select after the chain: P = exp2(-inf) = 0
+                if (key > q0 + q + p.off) sa[x] = kNegInf;
+            }
             const float pr = exp2f((sa[x] + sL[q]) * c);
             sa[x] = pr;                          // P
             pa[x] = pr * (pa[x] + sD[q]);        // dS
@@ -409,7 +426,7 @@ __global__ __launch_bounds__(256) void bwd_dkdv_f32(BwdParams p) {
     }
 }
 
-template <int D, int DV>
+template <int D, int DV, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void bwd_dq_f32(BwdParams p) {
     __shared__ float sK[D * kF32R], sV[DV * kF32R];
     const int N = p.N, Nk = p.Nk, d = p.d, dv = p.dv;
@@ -434,7 +451,9 @@ __global__ __launch_bounds__(256) void bwd_dq_f32(BwdParams p) {
     for (int i = 0; i < D / 32; ++i)
 #pragma unroll
         for (int x = 0; x < 16; ++x) aQ[i][x] = 0.0f;
-    for (int k0 = 0; k0 < Nk; k0 += kF32T) {
+    int kend = Nk;   // causal: keys up to the block's last real query's limit
+    if constexpr (CAUSAL) kend = min(Nk, min(q0 + 127, N - 1) + p.off + 1);
+    for (int k0 = 0; k0 < kend; k0 += kF32T) {
         __syncthreads();
         for (int i = tid; i < D * kF32T; i += 256) {
             const int k = i % kF32T, f = i / kF32T;
@@ -455,6 +474,9 @@ __global__ __launch_bounds__(256) void bwd_dq_f32(BwdParams p) {
         // lane (r, h): query r; register x: key acc_row(x, h)
 #pragma unroll
         for (int x = 0; x < 16; ++x) {
+            if constexpr (CAUSAL) {
+                if (k0 + acc_row(x, h) > qi + p.off) sa[x] = kNegInf;
+            }
             const float pr = exp2f((sa[x] + nlq) * c);
             pa[x] = pr * (pa[x] + ndq);          // dSᵀ
         }
@@ -480,6 +502,11 @@ __global__ __launch_bounds__(256) void bwd_dq_f32(BwdParams p) {
 template <int D, int DV>
 static hipError_t launch_f32_dd(const BwdParams& p, hipStream_t s) {
     const int64_t nq = ((int64_t)p.N + 127) / 128 * p.batch, nk = ((int64_t)p.Nk + 127) / 128 * p.batch;
+    if (p.causal) {
+        hipLaunchKernelGGL((bwd_dq_f32<D, DV, true>), dim3((unsigned)nq), dim3(256), 0, s, p);
+        hipLaunchKernelGGL((bwd_dkdv_f32<D, DV, true>), dim3((unsigned)nk), dim3(256), 0, s, p);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL((bwd_dq_f32<D, DV>), dim3((unsigned)nq), dim3(256), 0, s, p);
     hipLaunchKernelGGL((bwd_dkdv_f32<D, DV>), dim3((unsigned)nk), dim3(256), 0, s, p);
     return hipGetLastError();
@@ -567,7 +594,10 @@ __device__ void fused_combine(const BwdParams& p, int b, int qb) {
     }
 }
 
-template <class T, int D, int DV>
+// CAUSAL (fa_causal_bwd, never after bwd_fused: no guard, no combine): the key tiles end at
+// the block's last query's last visible tile, a wave skips the tiles past its own last query,
+// and S is selected to -inf on the tiles that straddle the wave's diagonal.
+template <class T, int D, int DV, bool CAUSAL = false>
 __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
     typedef typename Frag8<T>::type F8;
     constexpr int KB = D * 128, VB = DV * 128, STAGE = KB + VB;
@@ -618,7 +648,12 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
         dma_image<D>(krs, st, Nk, t * 64, wave, lane);
         dma_image<DV>(vrs, st + KB, Nk, t * 64, wave, lane);
     };
+    int wlim0 = 0;   // causal: the key limit (query row + off) of the wave's first query, a scalar
+    if constexpr (CAUSAL) wlim0 = qb * 128 + __builtin_amdgcn_readfirstlane(wave) * 32 + p.off;
     auto compute = [&](const char* st, int t) {
+        if constexpr (CAUSAL) {
+            if (t * 64 > wlim0 + 31) return;   // wave-uniform: no query of the wave sees the tile
+        }
         const char* kimg = st;
         const char* vimg = st + KB;
         const bool partial = (t + 1) * 64 > Nk;
@@ -636,6 +671,15 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
                 for (int x = 0; x < 16; ++x)
                     if (t * 64 + kb * 32 + (x & 7) + 8 * h + 16 * (x >> 3) >= Nk) sa[x] = kNegInf;
             }
+            if constexpr (CAUSAL) {
+                const int w0 = wlim0 - t * 64 - kb * 32;   // ... relative to the 32-key block
+                if (31 > w0) {
+                    const int lr = r - 8 * h + w0;           // key (x & 7) + 16 (x >> 3) + 8 h is hidden when > r + w0
+#pragma unroll
+                    for (int x = 0; x < 16; ++x)
+                        if ((x & 7) + 16 * (x >> 3) > lr) sa[x] = kNegInf;
+                }
+            }
             F8 dsf[2];
 #pragma unroll
             for (int x = 0; x < 16; ++x) {
@@ -649,7 +693,8 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
         }
     };
 
-    const int NT = (Nk + 63) / 64;
+    int NT = (Nk + 63) / 64;
+    if constexpr (CAUSAL) NT = min(NT, (min(qb * 128 + 127, N - 1) + p.off) / 64 + 1);
     char* const st0 = smem;
     char* const st1 = smem + STAGE;
     fill(st0, 0);
@@ -674,7 +719,11 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
     }
 }
 
-template <class T, int D, int DV>
+// CAUSAL: the query tiles (and the row-constant double buffer) begin at the first tile that
+// sees the block's first key, a wave skips the tiles before its own first key, and S is
+// selected to -inf after the MFMA chain (the accumulators start from the row constants) on
+// the tiles that straddle the wave's diagonal.
+template <class T, int D, int DV, bool CAUSAL = false>
 __global__ __launch_bounds__(256, 2) void bwd_dkdv_fast(BwdParams p) {
     typedef typename Frag8<T>::type F8;
     constexpr int QB = D * 128, OB = DV * 128, STAGE = QB + OB + 512;
@@ -729,7 +778,12 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_fast(BwdParams p) {
         dma_image<D>(qrs, st, N, t * 64, wave, lane);
         dma_image<DV>(ors, st + QB, N, t * 64, wave, lane);
     };
-    auto compute = [&](const char* st) {
+    int wk0 = 0;   // causal: the wave's first key minus off (the first query that sees it), a scalar
+    if constexpr (CAUSAL) wk0 = kblk * 128 + __builtin_amdgcn_readfirstlane(wave) * 32 - p.off;
+    auto compute = [&](const char* st, int t) {
+        if constexpr (CAUSAL) {
+            if (t * 64 + 63 < wk0) return;   // wave-uniform: no query of the tile sees the wave's keys
+        }
         const char* qimg = st;
         const char* oimg = st + QB;
         const float* rl = (const float*)(st + QB + OB);      // −lse[64], then −D[64]
@@ -750,6 +804,18 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_fast(BwdParams p) {
             for (int s = 0; s < D / 16; ++s) sa = mfma32x32x16(rd.tr(qimg, u, s), kf[s], sa);
 #pragma unroll
             for (int s = 0; s < DV / 16; ++s) dp = mfma32x32x16(rd.tr(oimg, u, s), vf[s], dp);
+            if constexpr (CAUSAL) {
+                const int q0 = t * 64 + u * 32 - wk0;   // the 32-query block's first row, relative to the wave's first key
+                if (q0 < 31) {                          // that row misses the wave's last key
+                    // query row (x & 7) + 16 (x >> 3) + 8 h misses key r when < r - q0; r and h rebuilt
+                    // from the lane id here (7 fewer spilled registers at d = dv = 128 than from r, h)
+                    const int ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+                    const int lk = (ln & 31) - 8 * (ln >> 5) - q0;
+#pragma unroll
+                    for (int x = 0; x < 16; ++x)
+                        if ((x & 7) + 16 * (x >> 3) < lk) sa[x] = kNegInf;
+                }
+            }
             F8 pf[2], dsf[2];
 #pragma unroll
             for (int x = 0; x < 16; ++x) {
@@ -771,20 +837,22 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_fast(BwdParams p) {
     const int NT = (N + 63) / 64;
     char* const st0 = smem;
     char* const st1 = smem + STAGE;
-    load_rowc(0);
-    fill(st0, 0);
+    int t0 = 0;   // causal: the first query tile that sees the block's first key (< NT: see DESIGN §2.7)
+    if constexpr (CAUSAL) t0 = min(max(0, kblk * 128 - p.off) / 64, NT - 1);
+    load_rowc(t0);
+    fill(st0, t0);
     store_rowc(st0);
     __syncthreads();
-    for (int t = 0; t < NT; t += 2) {
+    for (int t = t0; t < NT; t += 2) {
         load_rowc(min(t + 1, NT - 1));
         fill(st1, min(t + 1, NT - 1));
-        compute(st0);
+        compute(st0, t);
         store_rowc(st1);
         __syncthreads();
         if (t + 1 < NT) {
             load_rowc(min(t + 2, NT - 1));
             fill(st0, min(t + 2, NT - 1));
-            compute(st1);
+            compute(st1, t + 1);
             store_rowc(st0);
             __syncthreads();
         }
@@ -1547,6 +1615,15 @@ thread_local int g_bwd_xcd = -1;            // bwd_fused: one XCD per slab where
 
 template <class T, int D, int DV>
 static hipError_t launch_fast_dd(BwdParams p, hipStream_t s) {
+    if (p.causal) {   // always the two passes: no atomics, no hand-off
+        p.nblk = (p.N + 127) / 128;
+        p.total_wg = p.nblk * p.batch;
+        hipLaunchKernelGGL((bwd_dq_fast<T, D, DV, true>), dim3((unsigned)p.total_wg), dim3(256), 0, s, p);
+        p.nblk = (p.Nk + 127) / 128;
+        p.total_wg = p.nblk * p.batch;
+        hipLaunchKernelGGL((bwd_dkdv_fast<T, D, DV, true>), dim3((unsigned)p.total_wg), dim3(256), 0, s, p);
+        return hipGetLastError();
+    }
     const bool fused = p.part != nullptr;
     if (fused) {   // single pass; dQ pass below only after a hand-off timeout
         p.total_wg = p.nkb * p.batch;
@@ -1672,6 +1749,14 @@ size_t dense_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t 
     return kBwdHdrBytes + (size_t)(2 * rows * batch * sizeof(float) + 256) + (pl.on ? pl.bytes + 256 : 0) + fz.bytes;
 }
 
+// fa_causal_bwd: header, row statistics, pad plan; never the single pass's running sums
+size_t causal_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
+    if (dtype == FA_DTYPE_F64) return kBwdHdrBytes + (size_t)(2 * N * batch * sizeof(double) + 256);
+    const BwdPad pl = pad_plan(dtype, N, Nk, d, dv, batch);
+    const int64_t rows = pl.on ? pl.Np : N;
+    return kBwdHdrBytes + (size_t)(2 * rows * batch * sizeof(float) + 256) + (pl.on ? pl.bytes + 256 : 0);
+}
+
 // dst (Np, Cp, B) <- src (N, C, B), zero-filled
 template <class T>
 __global__ __launch_bounds__(256) void bwd_pad(const T* __restrict__ src, T* __restrict__ dst, int N, int C,
@@ -1732,6 +1817,13 @@ static hipError_t launch_generic(const BwdParams& p, hipStream_t s) {
     const size_t sm_dq = sizeof(A) * (rows + kGT * (kGT + 1));
     const size_t sm_kv = sizeof(A) * (rows + 2 * kGT * (kGT + 1));
     // > 64 KiB of dynamic LDS at d = dv = 128 (gfx950 has 160 KiB per CU)
+    if (p.causal) {
+        (void)hipFuncSetAttribute((const void*)bwd_generic_dq<T, A, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_dq);
+        (void)hipFuncSetAttribute((const void*)bwd_generic_dkdv<T, A, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_kv);
+        hipLaunchKernelGGL((bwd_generic_dq<T, A, true>), dim3((unsigned)nq), dim3(kGThreads), sm_dq, s, p);
+        hipLaunchKernelGGL((bwd_generic_dkdv<T, A, true>), dim3((unsigned)nk), dim3(kGThreads), sm_kv, s, p);
+        return hipGetLastError();
+    }
     (void)hipFuncSetAttribute((const void*)bwd_generic_dq<T, A>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_dq);
     (void)hipFuncSetAttribute((const void*)bwd_generic_dkdv<T, A>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_kv);
     hipLaunchKernelGGL((bwd_generic_dq<T, A>), dim3((unsigned)nq), dim3(kGThreads), sm_dq, s, p);
@@ -1814,12 +1906,22 @@ int launch_dense_bwd(const DenseBwdArgs& a, hipStream_t s, const char** why) {
         *why = "head dimension exceeds the compiled maximum (128)";
         return FA_ERR_UNSUPPORTED;
     }
+    if (a.causal && a.Nk < a.N) {
+        *why = "causal attention needs Nk >= N (a query would see no key)";
+        return FA_ERR_UNSUPPORTED;
+    }
     if (a.N * a.d > INT32_MAX || a.Nk * a.d > INT32_MAX || a.N * a.dv > INT32_MAX ||
         a.Nk * a.dv > INT32_MAX || a.N * a.batch > INT32_MAX / 2 || a.Nk * a.batch > INT32_MAX / 2) {
         *why = "extent exceeds 2^31 elements";
         return FA_ERR_UNSUPPORTED;
     }
+    if (a.causal && a.workspace_bytes < causal_bwd_workspace(a.dtype, a.N, a.Nk, a.d, a.dv, a.batch)) {
+        *why = "workspace smaller than fa_causal_bwd_workspace()";
+        return FA_ERR_WORKSPACE;
+    }
     BwdParams p;
+    p.causal = a.causal ? 1 : 0;
+    p.off = a.causal ? (int)(a.Nk - a.N) : 0;   // from the caller's extents, also on the padded path
     p.Q = a.Q; p.K = a.K; p.V = a.V; p.O = a.O; p.dO = a.dO; p.l = a.l; p.m = a.m;
     p.dQ = a.dQ; p.dK = a.dK; p.dV = a.dV;
     const uintptr_t ws0 = ((uintptr_t)a.workspace + 255) & ~(uintptr_t)255;
@@ -1835,7 +1937,7 @@ int launch_dense_bwd(const DenseBwdArgs& a, hipStream_t s, const char** why) {
     if (a.dtype == FA_DTYPE_F64) {
         // Float64: row statistics recomputed in double (not from the float32 l, m),
         // then the SIMT passes in double
-        if (a.workspace_bytes < dense_bwd_workspace(a.dtype, a.N, a.Nk, a.d, a.dv, a.batch)) {
+        if (!a.causal && a.workspace_bytes < dense_bwd_workspace(a.dtype, a.N, a.Nk, a.d, a.dv, a.batch)) {
             *why = "workspace smaller than fa_dense_bwd_workspace()";
             return FA_ERR_WORKSPACE;
         }
@@ -1854,7 +1956,7 @@ int launch_dense_bwd(const DenseBwdArgs& a, hipStream_t s, const char** why) {
         p.scale64 = a.scale64 > 0.0 ? a.scale64 : (double)a.scale;
         const int rc = launch_f64_bwd_stats(a, nD, nlse, s, why);
         if (rc != FA_OK) return rc;
-        if ((e = launch_generic<double, double>(p, s)) != hipSuccess) {
+        if ((e = launch_generic<double, double>(p, s)) != hipSuccess) {   // (causal: its CAUSAL instantiations)
             *why = hipGetErrorString(e);
             return FA_ERR_HIP;
         }
@@ -1882,7 +1984,7 @@ int launch_dense_bwd(const DenseBwdArgs& a, hipStream_t s, const char** why) {
             *why = "workspace smaller than fa_dense_bwd_workspace()";
             return FA_ERR_WORKSPACE;
         }
-        const FusedPlan fz = fused_plan(a.dtype, pl.Np, pl.Nkp, pl.Dp, pl.DVp, B, s);
+        const FusedPlan fz = a.causal ? FusedPlan{} : fused_plan(a.dtype, pl.Np, pl.Nkp, pl.Dp, pl.DVp, B, s);
         if (fz.on && (size_t)(w - (char*)a.workspace) + fz.bytes <= a.workspace_bytes &&
             (e = fused_setup(p, fz, w, s)) != hipSuccess) {
             *why = hipGetErrorString(e);
@@ -1921,7 +2023,7 @@ int launch_dense_bwd(const DenseBwdArgs& a, hipStream_t s, const char** why) {
         }
         return FA_OK;
     }
-    if (fast) {
+    if (fast && !a.causal) {   // causal never takes the single pass (fa_hip.h: fa_causal_bwd)
         const FusedPlan fz = fused_plan(a.dtype, a.N, a.Nk, a.d, a.dv, a.batch, s);
         char* w = (char*)ws + al256((size_t)(2 * a.N * a.batch) * sizeof(float));
         if (fz.on && (size_t)(w - (char*)a.workspace) + fz.bytes <= a.workspace_bytes &&

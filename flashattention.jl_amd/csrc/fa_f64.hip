@@ -37,6 +37,7 @@ struct F64Params {
     double* nlse;   // STATS: −(m + ln l)/τ per query, raw dot-product units [batch][N]
     int N, Nk, d, dv, nqb;
     double scale;
+    int causal = 0, off = 0;   // CAUSAL instantiations: query i sees keys j <= i + off (off = Nk - N)
 };
 
 constexpr int kQB64 = 64;    // queries per workgroup (QB = 16 for grids smaller than the chip)
@@ -52,7 +53,7 @@ static size_t f64_lds_bytes(int d, int dv, bool stats, int QB) {
 
 // QB queries per workgroup, NG = 256/QB thread groups per query: group g scores
 // keys KPG·g .. KPG·g + KPG−1 of each tile and owns output channels g, g + NG, ….
-template <bool STATS, int QB>
+template <bool STATS, int QB, bool CAUSAL = false>
 __global__ __launch_bounds__(kTh64) void dense_fwd_f64(F64Params p) {
     constexpr int NG = kTh64 / QB, KPG = kKB64 / NG, OPER = kMaxHeadDim / NG;
     static_assert(KPG >= 1 && QB * NG == kTh64, "geometry");
@@ -78,7 +79,11 @@ __global__ __launch_bounds__(kTh64) void dense_fwd_f64(F64Params p) {
     for (int i = 0; i < OPER; ++i) o[i] = 0.0;
     double m_run = -__builtin_huge_val(), l_run = 0.0;
 
-    for (int k0 = 0; k0 < Nk; k0 += kKB64) {
+    // causal: keys up to the workgroup's last real query's limit; key 0 is visible to every
+    // query, so m_run is finite after the first tile and a masked score gives exp(-inf) = 0
+    int kend = Nk;
+    if constexpr (CAUSAL) kend = min(Nk, min(q0 + QB - 1, N - 1) + p.off + 1);
+    for (int k0 = 0; k0 < kend; k0 += kKB64) {
         __syncthreads();   // the previous tile's K / V / P readers are done
         for (int i = tid; i < kKB64 * d; i += kTh64) {
             const int f = i >> 5, k = i & 31;
@@ -104,7 +109,9 @@ __global__ __launch_bounds__(kTh64) void dense_fwd_f64(F64Params p) {
         double mx = -__builtin_huge_val();
 #pragma unroll
         for (int j = 0; j < KPG; ++j) {
-            s[j] = k0 + KPG * g + j < Nk ? s[j] * p.scale : -__builtin_huge_val();
+            bool vis = k0 + KPG * g + j < Nk;
+            if constexpr (CAUSAL) vis = vis && k0 + KPG * g + j <= q0 + qi + p.off;
+            s[j] = vis ? s[j] * p.scale : -__builtin_huge_val();
             mx = dmax(mx, s[j]);
         }
         red[g * QB + qi] = mx;
@@ -179,9 +186,13 @@ __global__ __launch_bounds__(256) void bwd_rowdot_f64(const double* __restrict__
     nD[idx] = -acc;
 }
 
-static bool f64_fits(int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, const char** why) {
+static bool f64_fits(int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, const char** why, int causal = 0) {
     if (d > kMaxHeadDim || dv > kMaxHeadDim) {
         *why = "head dimension exceeds the compiled maximum (128)";
+        return false;
+    }
+    if (causal && Nk < N) {
+        *why = "causal attention needs Nk >= N (a query would see no key)";
         return false;
     }
     if (N > INT32_MAX / 2 || Nk > INT32_MAX / 2 || (N + kQB64 - 1) / kQB64 * batch > INT32_MAX) {
@@ -195,6 +206,12 @@ template <bool STATS, int QB>
 static hipError_t launch_f64_qb(F64Params p, int64_t batch, hipStream_t s) {
     p.nqb = (p.N + QB - 1) / QB;
     const size_t lds = f64_lds_bytes(p.d, p.dv, STATS, QB);
+    if (p.causal) {
+        (void)hipFuncSetAttribute((const void*)dense_fwd_f64<STATS, QB, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds);
+        hipLaunchKernelGGL((dense_fwd_f64<STATS, QB, true>), dim3((unsigned)(p.nqb * batch)), dim3(kTh64), lds, s, p);
+        return hipGetLastError();
+    }
     (void)hipFuncSetAttribute((const void*)dense_fwd_f64<STATS, QB>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);
     hipLaunchKernelGGL((dense_fwd_f64<STATS, QB>), dim3((unsigned)(p.nqb * batch)), dim3(kTh64), lds, s, p);
@@ -209,13 +226,15 @@ static hipError_t launch_f64_kernel(const F64Params& p, int64_t batch, hipStream
 }
 
 int launch_dense_fwd_f64(const DenseArgs& a, hipStream_t s, const char** why) {
-    if (!f64_fits(a.N, a.Nk, a.d, a.dv, a.batch, why)) return FA_ERR_UNSUPPORTED;
+    if (!f64_fits(a.N, a.Nk, a.d, a.dv, a.batch, why, a.causal)) return FA_ERR_UNSUPPORTED;
     F64Params p;
     p.Q = (const double*)a.Q; p.K = (const double*)a.K; p.V = (const double*)a.V; p.O = (double*)a.O;
     p.l = a.l; p.m = a.m; p.nlse = nullptr;
     p.N = (int)a.N; p.Nk = (int)a.Nk; p.d = (int)a.d; p.dv = (int)a.dv;
     p.nqb = (int)((a.N + kQB64 - 1) / kQB64);
     p.scale = a.scale64 > 0.0 ? a.scale64 : (double)a.scale;
+    p.causal = a.causal ? 1 : 0;
+    p.off = a.causal ? (int)(a.Nk - a.N) : 0;
     const hipError_t e = launch_f64_kernel<false>(p, a.batch, s);
     if (e != hipSuccess) {
         *why = hipGetErrorString(e);
@@ -225,13 +244,15 @@ int launch_dense_fwd_f64(const DenseArgs& a, hipStream_t s, const char** why) {
 }
 
 int launch_f64_bwd_stats(const DenseBwdArgs& a, double* nD, double* nlse, hipStream_t s, const char** why) {
-    if (!f64_fits(a.N, a.Nk, a.d, a.dv, a.batch, why)) return FA_ERR_UNSUPPORTED;
+    if (!f64_fits(a.N, a.Nk, a.d, a.dv, a.batch, why, a.causal)) return FA_ERR_UNSUPPORTED;
     F64Params p;
     p.Q = (const double*)a.Q; p.K = (const double*)a.K; p.V = nullptr; p.O = nullptr;
     p.l = nullptr; p.m = nullptr; p.nlse = nlse;
     p.N = (int)a.N; p.Nk = (int)a.Nk; p.d = (int)a.d; p.dv = (int)a.dv;
     p.nqb = (int)((a.N + kQB64 - 1) / kQB64);
     p.scale = a.scale64 > 0.0 ? a.scale64 : (double)a.scale;
+    p.causal = a.causal ? 1 : 0;
+    p.off = a.causal ? (int)(a.Nk - a.N) : 0;
     hipError_t e = launch_f64_kernel<true>(p, a.batch, s);
     if (e == hipSuccess) {
         const int64_t total = a.N * a.batch;

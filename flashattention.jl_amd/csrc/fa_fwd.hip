@@ -67,6 +67,7 @@ namespace fa {
 thread_local int g_fwd_variant = 0;
 thread_local int g_fwd_last_path = 0;   // fa_debug_fwd_last_path: 30 when the last fast launch ran fa_fwd_p4  // 0: auto; 4..7: forced geometry (benchmark knob, fa_debug_set_fwd_variant)
 thread_local float g_fwd_rescale_log2 = kRescaleLog2;  // fa_debug_set_rescale_threshold (accuracy tests)
+thread_local int g_causal_rev = 2;   // causal fast forward: launch order of the query blocks (fa_debug_set_causal_order)
 
 // FwdParams: fa_fwd_params.h (shared with fa_fwd_pipe.hip)
 
@@ -113,10 +114,19 @@ __device__ __forceinline__ unsigned pack_scaled(float a, float b, float s) {
     }
 }
 
+// Causal launches (fa_causal_fwd): query i sees keys j <= i + off, off = Nk - N >= 0, so key 0
+// is visible to every query and tile 0 is never skipped: the running max is finite after
+// tile 0, a row masked whole in a later tile has tile max -inf, leaves the running max alone
+// and gets P = exp2(-inf) = 0.  Tiles of `bn` keys a workgroup whose last query row is
+// q_last needs: up to the last visible key of its last real query.
+__device__ __forceinline__ int causal_ntiles(int nt, int q_last, int N, int off, int bn) {
+    return min(nt, (min(q_last, N - 1) + off) / bn + 1);
+}
+
 // --------------------------------------------------------------------------
 // bf16 / fp16 forward (v_mfma_f32_32x32x16_{bf16,f16})
 // --------------------------------------------------------------------------
-template <class T, int D, int DV>
+template <class T, int D, int DV, bool CAUSAL = false>
 __global__ __launch_bounds__(kThreads) void dense_fwd_generic(FwdParams p) {
     typedef typename Frag8<T>::type F8;
     typedef typename Frag8<T>::half F4;
@@ -200,7 +210,9 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic(FwdParams p) {
         }
     };
 
-    const int ntiles = (Nk + kBN - 1) / kBN;
+    int ntiles = (Nk + kBN - 1) / kBN;
+    if constexpr (CAUSAL)   // tiles up to the block's last query's last visible key (causal_ntiles)
+        ntiles = causal_ntiles(ntiles, qb * kBM + kBM - 1, N, (Nk - N), kBN);
     gload(0);
     lstore();
     __syncthreads();
@@ -235,6 +247,17 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic(FwdParams p) {
                     const int kt = kb * 32 + (x & 3) + 4 * ((x >> 2) & 1) + 8 * h + 16 * (x >> 3);
                     if (key0 + kt >= Nk) sacc[kb][x] = kNegInf;
                 }
+        }
+        if constexpr (CAUSAL) {   // keys past the lane's query + off (tiles that straddle the wave's diagonal)
+            if (key0 + kBN - 1 > qb * kBM + wave * 32 + (Nk - N)) {
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                    for (int x = 0; x < 16; ++x) {
+                        const int kt = kb * 32 + (x & 3) + 4 * ((x >> 2) & 1) + 8 * h + 16 * (x >> 3);
+                        if (key0 + kt > qi + (Nk - N)) sacc[kb][x] = kNegInf;
+                    }
+            }
         }
 
         // ---- online softmax (raw dot-product units; exp2 with folded scale) ----
@@ -304,7 +327,7 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic(FwdParams p) {
 // --------------------------------------------------------------------------
 // fp32 forward (exact f32 MFMA v_mfma_f32_32x32x2_f32)
 // --------------------------------------------------------------------------
-template <int D, int DV>
+template <int D, int DV, bool CAUSAL = false>
 __global__ __launch_bounds__(kThreads) void dense_fwd_generic_f32(FwdParams p) {
     constexpr int KROWF = kBN;       // K image [D][64] floats
     constexpr int VROWF = kBN + 1;   // V image [DV][65] floats (pad → conflict-free column reads)
@@ -371,7 +394,9 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic_f32(FwdParams p) {
         }
     };
 
-    const int ntiles = (Nk + kBN - 1) / kBN;
+    int ntiles = (Nk + kBN - 1) / kBN;
+    if constexpr (CAUSAL)   // tiles up to the block's last query's last visible key (causal_ntiles)
+        ntiles = causal_ntiles(ntiles, qb * kBM + kBM - 1, N, (Nk - N), kBN);
     gload(0);
     lstore();
     __syncthreads();
@@ -397,6 +422,15 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic_f32(FwdParams p) {
 #pragma unroll
                 for (int x = 0; x < 16; ++x)
                     if (key0 + kb * 32 + acc_row(x, h) >= Nk) sacc[kb][x] = kNegInf;
+        }
+        if constexpr (CAUSAL) {
+            if (key0 + kBN - 1 > qb * kBM + wave * 32 + (Nk - N)) {
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                    for (int x = 0; x < 16; ++x)
+                        if (key0 + kb * 32 + acc_row(x, h) > qi + (Nk - N)) sacc[kb][x] = kNegInf;
+            }
         }
 
         float mt = kNegInf;
@@ -483,8 +517,14 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic_f32(FwdParams p) {
 // barrier per tile, lazy rescale, branch-free buffer loads).  The partial-tile
 // V zeroing runs only on the last tile.
 // --------------------------------------------------------------------------
-template <class T, int D, int DV, int NW, int BN, int NQB, bool SPLIT = false, bool WIDE = false>
+//
+// CAUSAL (fa_causal_fwd; never with SPLIT): the workgroup's tiles end at its last query's
+// last visible key; loads, LDS stores and the barrier stay workgroup-uniform; a wave whose
+// last query is before a tile's first key skips that tile's compute, and the per-element
+// select runs only on tiles that straddle the wave's diagonal (both tests wave-uniform).
+template <class T, int D, int DV, int NW, int BN, int NQB, bool SPLIT = false, bool WIDE = false, bool CAUSAL = false>
 __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
+    static_assert(!(CAUSAL && SPLIT), "causal launches never split the keys");
     typedef typename Frag8<T>::type F8;
     typedef typename Frag8<T>::half F4;
     constexpr int NTH = 64 * NW;
@@ -524,6 +564,17 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
     int lid = xcd_remap(blockIdx.x, p.total_wg);
     const int split = SPLIT ? lid % p.nsplit : 0;
     if (SPLIT) lid /= p.nsplit;
+    if constexpr (CAUSAL) {   // launch order of the query blocks (A/B in DESIGN §2.7)
+        if (p.causal & 4) {
+            // block-major inside an XCD's share of the grid (consecutive ids, xcd_remap): the
+            // last (heaviest) block of each of its slabs first, then the one before, ...
+            const int per = p.total_wg >> 3, ns = per / p.nqb;
+            const int base = lid / per * per, loc = lid - base;
+            lid = base + (loc % ns) * p.nqb + (p.nqb - 1 - loc / ns);
+        } else if (p.causal & 2) {   // slab-major, a slab's heaviest block first
+            lid = lid / p.nqb * p.nqb + (p.nqb - 1 - lid % p.nqb);
+        }
+    }
     const int b = lid / p.nqb;
     const int qb = lid - b * p.nqb;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -553,7 +604,10 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
     const int NT = (Nk + BN - 1) / BN;
     const bool ragged = (Nk % BN) != 0;
     // key tiles [jt0, jt1) of this workgroup (all tiles unless split-KV)
-    const int jt0 = SPLIT ? split * p.tps : 0, jt1 = SPLIT ? min(NT, jt0 + p.tps) : NT;
+    // (causal: up to the last tile any of the workgroup's queries sees)
+    const int jt0 = SPLIT ? split * p.tps : 0;
+    int jt1 = SPLIT ? min(NT, jt0 + p.tps) : NT;
+    if constexpr (CAUSAL) jt1 = causal_ntiles(NT, qb * BM + BM - 1, N, (Nk - N), BN);
 
     u32x4 kreg[KCH], vreg[VCH];
     auto gload = [&](int j) {
@@ -673,6 +727,28 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
                         if (key0 + kt >= Nk) sacc[u][kb][x] = kNegInf;
                     }
         }
+        if constexpr (CAUSAL) {
+            // a select, not a bias; only on tiles with a key past the wave's first query's limit
+            // (it can meet the ragged mask above in one tile)
+            // w0: the key limit (query row + off) of the wave's first query, relative to the tile, in
+            // a scalar register; the lane's part (r - 8 h) is rebuilt from the lane id here, so
+            // the mask keeps no vector register alive across the loop
+            const int w0 = qb * BM + __builtin_amdgcn_readfirstlane(wave) * NQB * 32 + (Nk - N) - j * BN;
+            if (BN - 1 > w0) {
+                const int ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+                const int lr = (ln & 31) - 8 * (ln >> 5) + w0;
+#pragma unroll
+                for (int u = 0; u < NQB; ++u)
+#pragma unroll
+                    for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+                        for (int x = 0; x < 16; ++x) {
+                            // key ktc + 32 u + 8 h of the tile is hidden from the wave's query row 32 u + r
+                            const int ktc = kb * 32 + (x & 3) + 4 * ((x >> 2) & 1) + 16 * (x >> 3) - 32 * u;
+                            if (ktc > lr) sacc[u][kb][x] = kNegInf;
+                        }
+            }
+        }
         F8 pf[NQB][NKB][2];
 #pragma unroll
         for (int u = 0; u < NQB; ++u) {
@@ -683,7 +759,13 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
             const float mt = (FA_FWD_ABL & 4) ? sacc[u][0][0] : lane_max<NKB>(sacc[u]);
             m_true[u] = vmax(m_true[u], mt);
             if (__builtin_amdgcn_ballot_w64(mt > m_used[u] + thr_raw) != 0) {
-                const float m_new = fmaxf(m_used[u], swap_halves_max(mt));
+                float m_new = fmaxf(m_used[u], swap_halves_max(mt));
+                if constexpr (CAUSAL) {
+                    // only the rows that passed the threshold themselves move (the others get
+                    // alpha = 2^0 = 1, exact): a row's bits then depend on its own visible
+                    // scores alone, not on what a later row of the wave sees
+                    if (!(m_new > m_used[u] + thr_raw)) m_new = m_used[u];
+                }
                 const float alpha = exp2_fast((m_used[u] - m_new) * c);
                 l_run[u] *= alpha;
 #pragma unroll
@@ -738,14 +820,24 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
             }
     }
     FA_FWD_STAMP(1);
+    int wlast = 0;   // causal: the key limit (query row + off) of the wave's last query, a scalar
+    if constexpr (CAUSAL) wlast = qb * BM + (__builtin_amdgcn_readfirstlane(wave) + 1) * NQB * 32 - 1 + (Nk - N);
     for (int j = jt0; j < jt1; j += 2) {
         gload(min(j + 1, jt1 - 1));
-        compute(buf0, buf0 + KBYTES, j);
+        if constexpr (CAUSAL) {   // only if some query of the wave sees the tile (wave-uniform)
+            if (j * BN <= wlast) compute(buf0, buf0 + KBYTES, j);
+        } else {
+            compute(buf0, buf0 + KBYTES, j);
+        }
         lstore(buf1, min(j + 1, jt1 - 1));
         __syncthreads();
         if (j + 1 < jt1) {
             gload(min(j + 2, jt1 - 1));
-            compute(buf1, buf1 + KBYTES, j + 1);
+            if constexpr (CAUSAL) {
+                if ((j + 1) * BN <= wlast) compute(buf1, buf1 + KBYTES, j + 1);
+            } else {
+                compute(buf1, buf1 + KBYTES, j + 1);
+            }
             lstore(buf0, min(j + 2, jt1 - 1));
             __syncthreads();
         }
@@ -883,6 +975,18 @@ __global__ __launch_bounds__(512, 1) void dense_fwd_w8q2_split(FwdParams p) { de
 template <class T, int D, int DV>
 __global__ __launch_bounds__(512, 1) void dense_fwd_w8b64_split(FwdParams p) { dense_fwd_tiled<T, D, DV, 8, 64, 1, true>(p); }
 
+// causal instantiations of the four default geometries (fa_causal_fwd; no split-KV, no fa_fwd_p4)
+template <class T, int D, int DV>
+__global__ __launch_bounds__(512, 1) void causal_fwd_w8b64(FwdParams p) { dense_fwd_tiled<T, D, DV, 8, 64, 1, false, false, true>(p); }
+template <class T, int D, int DV>
+__global__ __launch_bounds__(512, 1) void causal_fwd_w8q2(FwdParams p) { dense_fwd_tiled<T, D, DV, 8, 64, 2, false, false, true>(p); }
+template <class T, int D, int DV>
+__global__ __launch_bounds__(512, 1) void causal_fwd_w8q2_wide(FwdParams p) {
+    dense_fwd_tiled<T, D, DV, 8, 64, 2, false, (D <= 64 && DV <= 64), true>(p);   // the launcher picks it only there
+}
+template <class T, int D, int DV>
+__global__ __launch_bounds__(512, 1) void causal_fwd_w8b64_wide(FwdParams p) { dense_fwd_tiled<T, D, DV, 8, 64, 1, false, true, true>(p); }
+
 // Split-KV combine: O = Σ_s o_s·2^(c(m_s − m)) / Σ_s l_s·2^(c(m_s − m)), m = max_s m_s
 // (fixed split order: deterministic).  One thread per output element.
 template <class T>
@@ -947,6 +1051,46 @@ static hipError_t launch_dv(const FwdParams& p, int DVc, dim3 grid, hipStream_t 
     // one wave per SIMD, persistent (fa_fwd_p4.hip): the default at d = dv = 128 (5-8 %
     // over the 8-wave kernel, bitwise equal: profiles/r04_fwd_p4_default_d128_ab.log);
     // at 64 the 8-wave kernel stays (p4 is 15 % slower there); variant 30 forces it
+    if (p.causal) {
+        // causal: the default geometry of the head-dim class (fast), else the generic kernel;
+        // fa_debug_set_fwd_variant does not apply
+        if (p.fast) {
+            const bool q2 = D <= 64 && DVc <= 64;
+            FwdParams q = p;
+            q.nqb = (q.N + (q2 ? 512 : 256) - 1) / (q2 ? 512 : 256);
+            q.total_wg = q.nqb * q.batch;
+            // order 2 needs every XCD's share of the grid to hold whole slabs
+            if (g_causal_rev == 2 && q.total_wg % 8 == 0 && (q.total_wg / 8) % q.nqb == 0) q.causal = 1 | 4;
+            const dim3 g2((unsigned)q.total_wg), blk(512);
+#define FA_LAUNCH_C(KER)                                                                \
+            switch (DVc) {                                                              \
+                case 32: hipLaunchKernelGGL((KER<T, D, 32>), g2, blk, 0, s, q); break;  \
+                case 64: hipLaunchKernelGGL((KER<T, D, 64>), g2, blk, 0, s, q); break;  \
+                case 128: hipLaunchKernelGGL((KER<T, D, 128>), g2, blk, 0, s, q); break; \
+                default: return hipErrorInvalidValue;                                   \
+            }
+            // (the two-query-block kernels are instantiated for d, dv <= 64 only: they spill above)
+#define FA_LAUNCH_C2(KER)                                                               \
+            if constexpr (D <= 64) {                                                    \
+                if (DVc == 32) hipLaunchKernelGGL((KER<T, D, 32>), g2, blk, 0, s, q);   \
+                else hipLaunchKernelGGL((KER<T, D, 64>), g2, blk, 0, s, q);             \
+            }
+            if (q2 && p.wide) { FA_LAUNCH_C2(causal_fwd_w8q2_wide) }
+            else if (q2) { FA_LAUNCH_C2(causal_fwd_w8q2) }
+            else if (p.wide) { FA_LAUNCH_C(causal_fwd_w8b64_wide) }
+            else { FA_LAUNCH_C(causal_fwd_w8b64) }
+#undef FA_LAUNCH_C2
+#undef FA_LAUNCH_C
+            return hipGetLastError();
+        }
+        switch (DVc) {
+            case 32: hipLaunchKernelGGL((dense_fwd_generic<T, D, 32, true>), grid, dim3(kThreads), 0, s, p); break;
+            case 64: hipLaunchKernelGGL((dense_fwd_generic<T, D, 64, true>), grid, dim3(kThreads), 0, s, p); break;
+            case 128: hipLaunchKernelGGL((dense_fwd_generic<T, D, 128, true>), grid, dim3(kThreads), 0, s, p); break;
+            default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
     if (p.fast && (g_fwd_variant == 30 || (g_fwd_variant == 0 && D == 128 && DVc == 128))) {
         hipError_t e = hipSuccess;
         if (launch_dense_fwd_p4(p, D, DVc, std::is_same<T, bf16>::value ? FA_DTYPE_BF16 : FA_DTYPE_F16, s, &e)) {
@@ -999,6 +1143,15 @@ static hipError_t launch_dv(const FwdParams& p, int DVc, dim3 grid, hipStream_t 
 }
 template <int D>
 static hipError_t launch_dv_f32(const FwdParams& p, int DVc, dim3 grid, hipStream_t s) {
+    if (p.causal) {
+        switch (DVc) {
+            case 32: hipLaunchKernelGGL((dense_fwd_generic_f32<D, 32, true>), grid, dim3(kThreads), 0, s, p); break;
+            case 64: hipLaunchKernelGGL((dense_fwd_generic_f32<D, 64, true>), grid, dim3(kThreads), 0, s, p); break;
+            case 128: hipLaunchKernelGGL((dense_fwd_generic_f32<D, 128, true>), grid, dim3(kThreads), 0, s, p); break;
+            default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
     switch (DVc) {
         case 32: hipLaunchKernelGGL((dense_fwd_generic_f32<D, 32>), grid, dim3(kThreads), 0, s, p); break;
         case 64: hipLaunchKernelGGL((dense_fwd_generic_f32<D, 64>), grid, dim3(kThreads), 0, s, p); break;
@@ -1056,6 +1209,10 @@ static size_t fwd_pad_bytes(int dtype, int64_t Nk, int64_t d, int64_t dv, int64_
 size_t dense_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
     return fwd_pad_bytes(dtype, Nk, d, dv, batch) + split_plan(dtype, N, Nk, d, dv, batch).bytes;
 }
+// fa_causal_fwd: the padded K / V copies only (causal launches never split the keys)
+size_t causal_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
+    return fwd_pad_bytes(dtype, Nk, d, dv, batch);
+}
 // dst (Np, C, B) <- src (N, C, B), zero rows n >= N
 template <class T>
 __global__ __launch_bounds__(256) void fwd_pad_keys(const T* __restrict__ src, T* __restrict__ dst, int N, int Np,
@@ -1073,6 +1230,10 @@ int launch_dense_fwd(const DenseArgs& a, hipStream_t s, const char** why) {
     const int Dc = head_dim_class(a.d), DVc = head_dim_class(a.dv);
     if (!Dc || !DVc) {
         *why = "head dimension exceeds the compiled maximum (128)";
+        return FA_ERR_UNSUPPORTED;
+    }
+    if (a.causal && a.Nk < a.N) {
+        *why = "causal attention needs Nk >= N (a query would see no key)";
         return FA_ERR_UNSUPPORTED;
     }
     if (a.N > INT32_MAX / 2 || a.Nk > INT32_MAX / 2 || a.N * a.d > INT32_MAX ||
@@ -1095,6 +1256,7 @@ int launch_dense_fwd(const DenseArgs& a, hipStream_t s, const char** why) {
     p.rescale_log2 = g_fwd_rescale_log2;
     p.batch = (int)a.batch;
     p.nsplit = 1; p.tps = 0; p.opart = p.lpart = p.mpart = nullptr;
+    p.causal = a.causal ? (g_causal_rev ? 3 : 1) : 0;   // (launch_dv turns order 2 into bit 2 where it applies)
     const int epc = a.dtype == FA_DTYPE_F32 ? 4 : 8;
     p.ldk = (int)a.Nk;
     p.fast = (a.Nk % epc == 0) && aligned16(a.K) && aligned16(a.V);
@@ -1131,7 +1293,7 @@ int launch_dense_fwd(const DenseArgs& a, hipStream_t s, const char** why) {
     // (not when fa_fwd_p4's own 256-row blocks already fill the chip)
     const bool p4_fills = (g_fwd_variant == 30 || (g_fwd_variant == 0 && Dc == 128 && DVc == 128)) &&
                           (a.N + 255) / 256 * a.batch >= device_cus(s);
-    if (p.fast && (g_fwd_variant == 0 || g_fwd_variant == 30) && !p4_fills && a.workspace) {
+    if (p.fast && !a.causal && (g_fwd_variant == 0 || g_fwd_variant == 30) && !p4_fills && a.workspace) {
         const SplitPlan sp = split_plan(a.dtype, a.N, a.Nk, a.d, a.dv, a.batch);
         if (sp.nsplit > 1 && a.workspace_bytes >= pad_bytes + sp.bytes) {
             auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };

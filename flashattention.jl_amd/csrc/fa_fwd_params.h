@@ -25,6 +25,13 @@ struct FwdParams {
     float rescale_log2;   // lazy-rescale threshold (log2 units): kRescaleLog2, or the debug knob
     int fast;  // K/V rows 16-B aligned and Nk a multiple of the chunk width
     int wide = 0;     // N % 8 == 0, Q and O 16-B aligned: Q / O staged through LDS (16-B accesses)
+    // causal launches (0: dense): bit 0 set, query i sees keys j <= i + off with off = Nk - N
+    // (N and Nk here are always the caller's extents: padded K / V copies change ldk only);
+    // bit 1: a slab's query blocks run last (heaviest) first; bit 2: block-major inside an
+    // XCD's share of the grid, heaviest first (dense_fwd_tiled).  One int, in the struct's tail
+    // padding: sizeof(FwdParams) and every existing kernel's argument layout stay as they were.
+    int causal = 0;
 };
+static_assert(sizeof(FwdParams) == 136, "fwd_split_combine's second argument follows the struct: keep its size");
 
 }  // namespace fa

@@ -18,6 +18,7 @@ struct DenseArgs {
     void* workspace = nullptr; // optional: padded K / V copies for ragged Nk (fa_dense_fwd_workspace)
     size_t workspace_bytes = 0;
     double scale64 = 0.0;      // Float64 kernels: τ resolved in double (0: use scale)
+    int causal = 0;            // fa_causal_fwd: query i sees keys j <= i + (Nk - N); 0: dense
 };
 
 struct DenseBwdArgs {
@@ -30,6 +31,7 @@ struct DenseBwdArgs {
     void* workspace;
     size_t workspace_bytes;
     double scale64 = 0.0;      // Float64 kernels: τ resolved in double (0: use scale)
+    int causal = 0;            // fa_causal_bwd: as DenseArgs::causal (always the two-pass form)
 };
 
 struct WindowGeom {
@@ -105,6 +107,11 @@ int launch_dense_fwd(const DenseArgs& a, hipStream_t s, const char** why);
 size_t dense_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch);
 size_t dense_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch);
 int launch_dense_bwd(const DenseBwdArgs& a, hipStream_t s, const char** why);
+// causal (DenseArgs / DenseBwdArgs with causal = 1): the forward's padded K / V copies only
+// (no split-KV part); the backward's header, row statistics and pad plan (never the single
+// pass's running sums).  Neither asks the device.
+size_t causal_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch);
+size_t causal_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch);
 int dense_bwd_handoff_status(const void* workspace, size_t workspace_bytes, hipStream_t s, int* status,
                              const char** why);
 // Float64 (fa_f64.hip): the forward, and the backward's row statistics in double
@@ -158,6 +165,7 @@ constexpr int kMaxHeadDim = 128;
 extern thread_local int g_fwd_variant;        // forward kernel variant
 extern thread_local int g_fwd_last_path;      // 30 when the last fast forward launch ran fa_fwd_p4
 extern thread_local float g_fwd_rescale_log2; // forward fast kernels: lazy-rescale threshold (log2 units)
+extern thread_local int g_causal_rev;         // causal fast forward: launch order of the query blocks (0, 1, 2: fa_debug_set_causal_order)
 extern thread_local int g_bwd_force_generic;  // backward: force the generic SIMT path
 extern thread_local int g_bwd_mode;           // backward MFMA path: 0 auto, 1 split passes, 2 single pass
 extern thread_local int g_bwd_l2local;        // single pass: running sums handed over in the XCD's L2

@@ -41,6 +41,7 @@ __all__ = [
     "windowed_fa", "block_fa",
     "windowed_fa_backward", "window_geometry", "circulant_fa", "circulant_fa_", "circulant_fa_backward",
     "circulant_dpa",
+    "causal_fa", "causal_fa_", "causal_fa_backward", "causal_dpa",
     "fused_softmax", "fused_softmax_", "DTYPES",
 ]
 
@@ -138,6 +139,18 @@ def lib() -> ctypes.CDLL:
                                        i64, i64, i64, i64, i64, f32, vp, ctypes.c_size_t, vp]
         L.fa_debug_last_circ_bwd_kernel.restype = ctypes.c_int
         L.fa_debug_last_circ_bwd_kernel.argtypes = []
+    if hasattr(L, "fa_causal_fwd"):
+        for wq in (L.fa_causal_fwd_workspace, L.fa_causal_bwd_workspace):
+            wq.restype = ctypes.c_size_t
+            wq.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64]
+        L.fa_causal_fwd.restype = ctypes.c_int
+        L.fa_causal_fwd.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, f32, vp,
+                                    ctypes.c_size_t, vp]
+        L.fa_causal_bwd.restype = ctypes.c_int
+        L.fa_causal_bwd.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                    i64, i64, i64, i64, i64, f32, vp, ctypes.c_size_t, vp]
+        L.fa_debug_set_causal_order.restype = ctypes.c_int
+        L.fa_debug_set_causal_order.argtypes = [ctypes.c_int]
     L.fa_softmax_workspace.restype = ctypes.c_size_t
     L.fa_softmax_workspace.argtypes = [i64, i64, i64, ctypes.c_int]
     L.fa_softmax.restype = ctypes.c_int
@@ -308,6 +321,108 @@ def dense_fa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float = 0
     return y, l, m
 
 
+# ----------------------------------------------------------------------------
+# causal dense
+# ----------------------------------------------------------------------------
+def _causal_extents(N: int, Nk: int) -> None:
+    """The C ABI's rule, raised before any device is touched."""
+    if Nk < N:
+        raise FlashAttentionError(FA_ERR_UNSUPPORTED,
+                                  f"causal attention needs Nk >= N (got N = {N}, Nk = {Nk}): a query would see no key")
+
+
+def causal_fa_(O: torch.Tensor, l: torch.Tensor, m: torch.Tensor,
+               Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor,
+               scale: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Causal ``dense_fa!``, in place: query i attends the keys j <= i + (Nk - N)
+    (bottom-right aligned: the last query sees every key; N == Nk is the lower
+    triangle).  Q (N, d, B), K (Nk, d, B), V (Nk, dv, B), O (N, dv, B); l, m (N, 1, B)
+    float32 over the visible keys.  Nk < N raises FlashAttentionError (unsupported)."""
+    for t in (O, l, m, Q, K, V):
+        _require(t.dim() == 3, "causal_fa! expects 3-D (N, d, batch) arrays")
+    N, d, B = Q.shape
+    Nk, dv = K.shape[0], V.shape[1]
+    _require(K.shape == (Nk, d, B), f"K has shape {tuple(K.shape)}, expected ({Nk}, {d}, {B})")
+    _require(V.shape == (Nk, dv, B), f"V has shape {tuple(V.shape)}, expected ({Nk}, {dv}, {B})")
+    _require(O.shape == (N, dv, B), f"O has shape {tuple(O.shape)}, expected ({N}, {dv}, {B})")
+    _require(l.shape == (N, 1, B) and m.shape == (N, 1, B), "l, m must be (N, 1, batch)")
+    _require(l.dtype == torch.float32 and m.dtype == torch.float32, "l, m must be float32")
+    code = _dtype_code(Q, K, V, O)
+    _causal_extents(N, Nk)
+    _device_check(Q, K, V, O, l, m)
+    Lb = lib()
+    nws = Lb.fa_causal_fwd_workspace(code, N, Nk, d, dv, B)
+    ws = _workspace(Q.device, nws) if nws else None
+    _check(Lb.fa_causal_fwd(code, _ptr(Q), _ptr(K), _ptr(V), _ptr(O), _ptr(l), _ptr(m),
+                            N, Nk, d, dv, B, float(scale), _ptr(ws), int(nws), _stream(Q)))
+    return O, l, m
+
+
+def causal_fa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float = 0.0):
+    """``causal_fa(q, k, v) -> (O, l, m)``: :func:`causal_fa_` on fresh outputs.
+    q (N, d, B), k (Nk, d, B), v (Nk, dv, B) with Nk >= N."""
+    _require(q.dim() == 3 and k.dim() == 3 and v.dim() == 3, "causal_fa expects 3-D (N, d, batch) arrays")
+    N, d, B = q.shape
+    O = jl_empty((N, v.shape[1], B), q.dtype, q.device)
+    l = jl_empty((N, 1, B), torch.float32, q.device)
+    m = jl_empty((N, 1, B), torch.float32, q.device)
+    return causal_fa_(O, l, m, q, k, v, scale)
+
+
+def causal_fa_backward(Q, K, V, O, dO, l, m, scale: float = 0.0):
+    """Backward of :func:`causal_fa`: returns ``(dQ, dK, dV)``.  O, l, m are the
+    forward's outputs.  Always the two-pass form (no atomics, no hand-off), so all
+    three gradients are bitwise reproducible; :func:`backward_handoff_status` reads
+    -1 after it."""
+    for t in (Q, K, V, O, dO, l, m):
+        _require(t.dim() == 3, "causal_fa_backward expects 3-D (N, d, batch) arrays")
+    N, d, B = Q.shape
+    Nk, dv = K.shape[0], V.shape[1]
+    _require(K.shape == (Nk, d, B) and V.shape == (Nk, dv, B), "K, V shapes disagree with Q")
+    _require(O.shape == (N, dv, B) and dO.shape == (N, dv, B), "O, dO must be (N, dv, batch)")
+    _require(l.shape == (N, 1, B) and m.shape == (N, 1, B), "l, m must be (N, 1, batch)")
+    _require(l.dtype == torch.float32 and m.dtype == torch.float32, "l, m must be float32")
+    code = _dtype_code(Q, K, V, O, dO)
+    _causal_extents(N, Nk)
+    _device_check(Q, K, V, O, dO, l, m)
+    dQ = jl_empty((N, d, B), Q.dtype, Q.device)
+    dK = jl_empty((Nk, d, B), Q.dtype, Q.device)
+    dV = jl_empty((Nk, dv, B), Q.dtype, Q.device)
+    L = lib()
+    nws = L.fa_causal_bwd_workspace(code, N, Nk, d, dv, B)
+    ws = _workspace(Q.device, nws, entry="causal_fa_backward")
+    _check(L.fa_causal_bwd(code, _ptr(Q), _ptr(K), _ptr(V), _ptr(O), _ptr(dO), _ptr(l), _ptr(m),
+                           _ptr(dQ), _ptr(dK), _ptr(dV), N, Nk, d, dv, B, float(scale),
+                           _ptr(ws), int(nws), _stream(Q)))
+    return dQ, dK, dV
+
+
+def causal_dpa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float = 0.0):
+    """``causal_dpa(q, k, v) -> (O, P)``: the materialising form of :func:`causal_fa`, in the
+    style of :func:`dense_dpa`: S = τ Q Kᵀ by a library GEMM, −∞ where j > i + (Nk − N),
+    P = softmax over the keys by this library's fa_softmax kernel (dims = 2; exactly 0 above
+    the diagonal), O = P V.  P is (N, Nk, B) in the input dtype; memory is O(N·Nk·B)."""
+    _require(q.dim() == 3 and k.dim() == 3 and v.dim() == 3, "causal_dpa expects 3-D (N, d, batch) arrays")
+    N, d, B = q.shape
+    Nk, dv = k.shape[0], v.shape[1]
+    _require(k.shape == (Nk, d, B) and v.shape == (Nk, dv, B),
+             "DimensionMismatch: k must match q's feature and batch dims, v k's token count and the batch dim")
+    _dtype_code(q, k, v)
+    _causal_extents(N, Nk)
+    _device_check(q, k, v)
+    tau = float(scale) if scale > 0 else 1.0 / math.sqrt(d)
+    Qr, Kr, Vr = _rm(q), _rm(k), _rm(v)       # [B][d][N], [B][d][Nk], [B][dv][Nk]
+    St = torch.bmm(Kr.transpose(1, 2), Qr)    # [B][Nk][N] = column-major (N, Nk, B): P's layout
+    St.mul_(tau)
+    j = torch.arange(Nk, device=q.device)[:, None]
+    i = torch.arange(N, device=q.device)[None, :]
+    St.masked_fill_((j > i + (Nk - N))[None], float("-inf"))
+    P = _rm(St)                               # (N, Nk, B) view
+    fused_softmax_(P, P, dims=2)
+    O = _rm(torch.bmm(Vr, St))                # [B][dv][N] = column-major (N, dv, B)
+    return O, P
+
+
 def circulant_fa_(O: torch.Tensor, l: torch.Tensor, m: torch.Tensor,
                   Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, W: int,
                   scale: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -443,7 +558,7 @@ def backward_handoff_status(device=None) -> int:
     stream = torch.cuda.current_stream(device)
     key = (device.type, device.index, stream.cuda_stream)
     buf = _WS.get(key)
-    _require(buf is not None and _WS_LAST.get(key) == "dense_fa_backward",
+    _require(buf is not None and _WS_LAST.get(key) in ("dense_fa_backward", "causal_fa_backward"),
              "the last call that used this stream's scratch buffer was not dense_fa_backward")
     st = ctypes.c_int(-2)
     _check(lib().fa_dense_bwd_handoff_status(_ptr(buf), buf.numel(), ctypes.c_void_p(stream.cuda_stream),

@@ -240,6 +240,115 @@ function dense_fa_backward(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3},
     return dense_fa_backward_f32(Q, K, V, O, dO, Float32.(l), Float32.(m), handoff)
 end
 
+# causal_fa!(O, l, m, Q, K, V) — causal dense attention (the reference has none; the mask of
+# NNlib.dot_product_attention, bottom-right aligned): query i attends the keys
+# j <= i + (Nk - N).  Nk < N is an error (some query would see no key).
+function causal_fa_f32!(O::ROCArray{T,3}, l::ROCArray{Float32,3}, m::ROCArray{Float32,3},
+                        Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3}) where {T}
+    N, d, B = size(Q)
+    Nk, dv = size(K, 1), size(V, 2)
+    size(K) == (Nk, d, B) || throw(DimensionMismatch("K"))
+    size(V) == (Nk, dv, B) || throw(DimensionMismatch("V"))
+    size(O) == (N, dv, B) || throw(DimensionMismatch("O"))
+    size(l) == (N, 1, B) && size(m) == (N, 1, B) || throw(DimensionMismatch("l, m must be (N, 1, batch)"))
+    nws = ccall((:fa_causal_fwd_workspace, libfa_hip), Csize_t,
+                (Cint, Int64, Int64, Int64, Int64, Int64), fa_dtype(T), N, Nk, d, dv, B)
+    with_workspace(nws) do ws
+        fa_check(ccall((:fa_causal_fwd, libfa_hip), Cint,
+                       (Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32},
+                        Int64, Int64, Int64, Int64, Int64, Cfloat, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+                       fa_dtype(T), Q, K, V, O, l, m, N, Nk, d, dv, B, 0f0, ws, nws, stream_ptr()))
+    end
+    return O, l, m
+end
+
+# l, m in another element type, staged in Float32 as dense_fa_staged! does
+function causal_fa_staged!(O::ROCArray{T,3}, l::ROCArray{S,3}, m::ROCArray{S,3},
+                           Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3}) where {T,S}
+    size(l) == size(m) || throw(DimensionMismatch("l, m"))
+    lf, mf = similar(l, Float32), similar(m, Float32)
+    causal_fa_f32!(O, lf, mf, Q, K, V)
+    l .= lf
+    m .= mf
+    return O, l, m
+end
+
+# Methods laid out as dense_fa!'s, so that no call is ambiguous: T data with Float32
+# statistics, one type T throughout, all Float32, any other statistics type S.
+function causal_fa!(O::ROCArray{T,3}, l::ROCArray{Float32,3}, m::ROCArray{Float32,3},
+                    Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3}) where {T}
+    return causal_fa_f32!(O, l, m, Q, K, V)
+end
+function causal_fa!(O::ROCArray{T,3}, l::ROCArray{T,3}, m::ROCArray{T,3},
+                    Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3}) where {T}
+    return causal_fa_staged!(O, l, m, Q, K, V)
+end
+function causal_fa!(O::ROCArray{Float32,3}, l::ROCArray{Float32,3}, m::ROCArray{Float32,3},
+                    Q::ROCArray{Float32,3}, K::ROCArray{Float32,3}, V::ROCArray{Float32,3})
+    return causal_fa_f32!(O, l, m, Q, K, V)
+end
+function causal_fa!(O::ROCArray{T,3}, l::ROCArray{S,3}, m::ROCArray{S,3},
+                    Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3}) where {T,S}
+    return causal_fa_staged!(O, l, m, Q, K, V)
+end
+
+# causal_fa(Q, K, V) -> (O, l, m), Float32 statistics
+function causal_fa(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3}) where {T}
+    N, B = size(Q, 1), size(Q, 3)
+    O = similar(Q, N, size(V, 2), B)
+    l = similar(Q, Float32, N, 1, B)
+    m = similar(Q, Float32, N, 1, B)
+    return causal_fa!(O, l, m, Q, K, V)
+end
+
+# causal_fa_backward(Q, K, V, O, dO, l, m) -> (dQ, dK, dV): always the two-pass form, all
+# three gradients bitwise reproducible
+function causal_fa_backward_f32(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3},
+                                O::ROCArray{T,3}, dO::ROCArray{T,3},
+                                l::ROCArray{Float32,3}, m::ROCArray{Float32,3}) where {T}
+    N, d, B = size(Q)
+    Nk, dv = size(K, 1), size(V, 2)
+    size(K) == (Nk, d, B) && size(V) == (Nk, dv, B) ||
+        throw(DimensionMismatch("K, V shapes disagree with Q"))
+    size(O) == (N, dv, B) && size(dO) == (N, dv, B) ||
+        throw(DimensionMismatch("O, dO must be (N, dv, batch)"))
+    size(l) == (N, 1, B) && size(m) == (N, 1, B) ||
+        throw(DimensionMismatch("l, m must be (N, 1, batch)"))
+    dQ, dK, dV = similar(Q), similar(K), similar(V)
+    nws = ccall((:fa_causal_bwd_workspace, libfa_hip), Csize_t,
+                (Cint, Int64, Int64, Int64, Int64, Int64), fa_dtype(T), N, Nk, d, dv, B)
+    with_workspace(nws) do ws
+        fa_check(ccall((:fa_causal_bwd, libfa_hip), Cint,
+                       (Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float32},
+                        Ptr{Float32}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+                        Int64, Int64, Int64, Int64, Int64, Cfloat, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+                       fa_dtype(T), Q, K, V, O, dO, l, m, dQ, dK, dV, N, Nk, d, dv, B, 0f0,
+                       ws, nws, stream_ptr()))
+    end
+    return dQ, dK, dV
+end
+
+function causal_fa_backward(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3},
+                            O::ROCArray{T,3}, dO::ROCArray{T,3},
+                            l::ROCArray{Float32,3}, m::ROCArray{Float32,3}) where {T}
+    return causal_fa_backward_f32(Q, K, V, O, dO, l, m)
+end
+function causal_fa_backward(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3},
+                            O::ROCArray{T,3}, dO::ROCArray{T,3},
+                            l::ROCArray{T,3}, m::ROCArray{T,3}) where {T}
+    return causal_fa_backward_f32(Q, K, V, O, dO, Float32.(l), Float32.(m))
+end
+function causal_fa_backward(Q::ROCArray{Float32,3}, K::ROCArray{Float32,3}, V::ROCArray{Float32,3},
+                            O::ROCArray{Float32,3}, dO::ROCArray{Float32,3},
+                            l::ROCArray{Float32,3}, m::ROCArray{Float32,3})
+    return causal_fa_backward_f32(Q, K, V, O, dO, l, m)
+end
+function causal_fa_backward(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3},
+                            O::ROCArray{T,3}, dO::ROCArray{T,3},
+                            l::ROCArray{S,3}, m::ROCArray{S,3}) where {T,S}
+    return causal_fa_backward_f32(Q, K, V, O, dO, Float32.(l), Float32.(m))
+end
+
 # windowed_fa(q, k, v, ws; stride, pad) — src/windowed.jl:3-23 (fused on the device)
 function windowed_fa(q::ROCArray{T,N}, k::ROCArray{T,N}, v::ROCArray{T,N}, windowsize;
                      stride=windowsize, pad=(windowsize - 1) ÷ 2) where {T,N}

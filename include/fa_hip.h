@@ -247,6 +247,64 @@ int fa_circulant_bwd(int dtype,
                      float scale, void* workspace, size_t workspace_bytes,
                      void* hip_stream);
 
+/* Causal dense attention (the reference has none; NNlib.dot_product_attention's
+ * causal mask, bottom-right aligned): query i attends the keys j <= i + off,
+ * off = Nk - N, so the last query sees every key (a KV cache's alignment) and
+ * N == Nk is the ordinary lower triangle.
+ *   Q (N, d, B), K (Nk, d, B), V (Nk, dv, B) -> O (N, dv, B); l, m (N, 1, B)
+ * float32 with the dense_fa! meaning, taken over the visible keys only.  The mask
+ * is a select (score := -Inf), not an added bias: a masked key's K values reach no
+ * result (inputs are assumed finite: a masked V is multiplied by P = 0).  dv != d,
+ * any d, dv <= fa_max_head_dim(), ragged N / Nk and all four dtypes are accepted, as
+ * for fa_dense_fwd_ws.  Checks, in order: null pointers, DimensionMismatch, head
+ * dims and Nk >= N (Nk < N, where some query would see no key, is
+ * FA_ERR_UNSUPPORTED), 32-bit extents, workspace; all before any launch.  N == 0
+ * or batch == 0 is a no-op.  The same tile bodies as the dense forward with the key
+ * loop cut at each workgroup's diagonal; causal launches never split the keys and
+ * never take the one-wave-per-SIMD kernel. */
+int fa_causal_fwd(int dtype,
+                  const void* Q, const void* K, const void* V,
+                  void* O, float* l, float* m,
+                  int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch,
+                  float scale, void* workspace, size_t workspace_bytes,
+                  void* hip_stream);
+
+/* Workspace bytes fa_causal_fwd needs (0 is a valid answer): the zero-padded K / V
+ * copies for bf16 / fp16 with Nk % 8 != 0, as fa_dense_fwd_ws, plus 256 B of slack
+ * so the workspace may start at any address.  No split-KV part. */
+size_t fa_causal_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d,
+                               int64_t dv, int64_t batch);
+
+/* Workspace bytes fa_causal_bwd needs: the 256-B header, the row statistics
+ * (8·N·batch bytes, double for FA_DTYPE_F64) and, for bf16 / fp16 shapes outside
+ * the MFMA kernels' set, the zero-padded copies, plus 256 B of slack so the
+ * workspace may start at any address.  Never the single pass's running sums, and
+ * independent of the device. */
+size_t fa_causal_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d,
+                               int64_t dv, int64_t batch);
+
+/* Causal backward: the chain rule of fa_causal_fwd over the visible keys,
+ *   P_ij = exp(s_ij - m_i)/l_i for j <= i + off (0 elsewhere), dV = P^T dO,
+ *   dP = dO V^T, D = rowsum(dO .* O), dS = P .* (dP - D), dQ = scale dS K,
+ *   dK = scale dS^T Q.
+ * O, l, m are fa_causal_fwd's outputs (FA_DTYPE_F64 recomputes the statistics in
+ * double and does not read l, m).  It always runs the two-pass form (a dQ pass whose
+ * key tiles end at the diagonal, a dK/dV pass whose query tiles begin there) and
+ * never fa_dense_bwd's single pass: the ordered dQ hand-off's rotated chains assume
+ * every member visits every slice, and under a causal mask the hand-off costs more
+ * than it saves.  The two passes need no atomics and no hand-off, so dQ, dK and dV
+ * are ALL bitwise reproducible.  The workspace header is written so that
+ * fa_dense_bwd_handoff_status on this workspace answers -1.  dQ, dK, dV are fully
+ * written.  Checks and empty inputs as fa_causal_fwd. */
+int fa_causal_bwd(int dtype,
+                  const void* Q, const void* K, const void* V,
+                  const void* O, const void* dO,
+                  const float* l, const float* m,
+                  void* dQ, void* dK, void* dV,
+                  int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch,
+                  float scale, void* workspace, size_t workspace_bytes,
+                  void* hip_stream);
+
 /* Standalone fused softmax, replaces
  *   fused_softmax!(P, S; dims)   reference src/fused_softmax.jl:1-41
  * (device versions src/cuda/fused_softmax.jl:11-314).  S, P: (M, N, batch)
