@@ -15,6 +15,7 @@
 
 #include "../../include/fa_hip.h"
 #include "fa_internal.h"
+#include "fa_windowed.h"   // the windowed plans (host functions; no kernel is instantiated here)
 
 namespace {
 
@@ -226,6 +227,28 @@ int fa_debug_set_win_composed(int v) {
     const int old = fa::g_win_force_composed;
     fa::g_win_force_composed = ((v >= 1 && v <= 6) || v == 10 || v == 12 || v == 13) ? v : 0;
     return old;
+}
+
+// Not part of the public header (tests): the kernel the windowed forward / backward picks
+// for a shape, as a fa::WinFwdKernel / fa::WinBwdKernel value (-1: invalid arguments).  The
+// mode (a fa_debug_set_win_composed value), the 16-B alignment facts of the tensors and the
+// CU count are arguments: nothing is read from the thread's knobs or the device.
+int fa_debug_win_fwd_plan(int dtype, int nspatial, const int64_t* spatial, int64_t d, int64_t dv, int64_t batch,
+                          int64_t ws, int64_t stride, int64_t pad, int mode, int qkv_aligned16, int y_aligned16) {
+    fa::WindowGeom g;
+    const char* why = "";
+    if (!valid_dtype(dtype) || d < 1 || dv < 1 || batch < 1) return -1;
+    if (make_geom(g, nspatial, spatial, ws, stride, pad, &why) != FA_OK) return -1;
+    return fa::win_fwd_plan(dtype, g, d, dv, batch, mode, qkv_aligned16 != 0, y_aligned16 != 0);
+}
+int fa_debug_win_bwd_plan(int dtype, int nspatial, const int64_t* spatial, int64_t d, int64_t dv, int64_t batch,
+                          int64_t ws, int64_t stride, int64_t pad, int mode, int in_aligned16, int grad_aligned16,
+                          int cus) {
+    fa::WindowGeom g;
+    const char* why = "";
+    if (!valid_dtype(dtype) || d < 1 || dv < 1 || batch < 1) return -1;
+    if (make_geom(g, nspatial, spatial, ws, stride, pad, &why) != FA_OK) return -1;
+    return fa::win_bwd_plan(dtype, g, d, dv, batch, mode, in_aligned16 != 0, grad_aligned16 != 0, fa::win_cus(cus));
 }
 
 // Not part of the public header: workgroups of the persistent strip backward (0 = one per

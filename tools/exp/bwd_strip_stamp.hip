@@ -16,7 +16,8 @@ __device__ unsigned long long g_stamp_ws[256];   // the strip counters' workspac
             if ((k) == 15) ::g_stamp_buf[fa_sid * 24 + 17] = __builtin_amdgcn_s_memrealtime(); \
         }                                                                                  \
     } while (0)
-#include "../../flashattention.jl_amd/csrc/fa_windowed.hip"
+#include "../../flashattention.jl_amd/csrc/fa_windowed_bwd.hip"
+namespace fa { thread_local int g_win_force_composed = 0; }   // defined by the forward file in the library
 
 extern "C" int bwd_stamp_run(const void* q, const void* k, const void* v, const void* y, const void* dy, float* l,
                              float* m, void* dq, void* dk, void* dv, int B, int mode, unsigned long long* host_out,
@@ -33,7 +34,7 @@ extern "C" int bwd_stamp_run(const void* q, const void* k, const void* v, const 
     a.workspace = ws; a.workspace_bytes = sizeof(unsigned long long) * 256;
     fa::g_win_force_composed = mode;
     const char* why = nullptr;
-    int rc = fa::windowed_bwd_rows<fa::bf16>(a, nullptr, &why);
+    int rc = fa::launch_windowed_bwd(a, nullptr, &why);
     fa::g_win_force_composed = 0;
     if (rc != 0) return 1;
     if (!host_out) return 0;

@@ -13,7 +13,7 @@ __device__ unsigned long long g_stamp_buf[8 * 16384];
             if ((k) == 5) ::g_stamp_buf[blockIdx.x * 8 + 7] = __builtin_amdgcn_s_memrealtime(); \
         }                                                                                  \
     } while (0)
-#include "../../flashattention.jl_amd/csrc/fa_windowed.hip"
+#include "../../flashattention.jl_amd/csrc/fa_windowed_fwd.hip"
 
 extern "C" int strip_stamp_run(const void* q, const void* k, const void* v, void* y, float* l, float* m, int B,
                                int mode, unsigned long long* host_out, int nwg_max, void* ws, size_t ws_bytes) {
@@ -24,11 +24,11 @@ extern "C" int strip_stamp_run(const void* q, const void* k, const void* v, void
     a.g.O[0] = 19; a.g.O[1] = 19; a.g.O[2] = 1; a.g.T = 49; a.g.L = 361; a.g.P = 128 * 128;
     a.d = 64; a.dv = 64; a.batch = B; a.scale = 0.125f;
     a.workspace = ws; a.workspace_bytes = ws_bytes;
-    const fa::WinDev g = fa::to_dev(a.g);
+    const char* why = nullptr;
     fa::g_win_force_composed = mode;
-    hipError_t e = fa::launch_rows1_dd<fa::bf16, 64, 64>(a, g, nullptr);
+    const int rc = fa::launch_windowed_fwd(a, nullptr, &why);
     fa::g_win_force_composed = 0;
-    if (e != hipSuccess) return 1;
+    if (rc != 0) return 1;
     if (!host_out) return 0;
     if (hipDeviceSynchronize() != hipSuccess) return 2;
     if (hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_stamp_buf), sizeof(unsigned long long) * 8 * nwg_max) != hipSuccess) return 3;

@@ -11,7 +11,9 @@ __device__ unsigned long long g_stamp_buf[8 * 16384];
             if ((k) == 5) ::g_stamp_buf[blockIdx.x * 8 + 7] = __builtin_amdgcn_s_memrealtime(); \
         }                                                                                  \
     } while (0)
-#include "../../flashattention.jl_amd/csrc/fa_windowed.hip"
+#include "../../flashattention.jl_amd/csrc/fa_windowed_fwd.hip"
+#include "../../flashattention.jl_amd/csrc/fa_windowed_bwd.hip"
+// (the forward file defines g_win_force_composed, the backward file g_win_bwd_grid)
 
 extern "C" int stamp_run(const void* q, const void* k, const void* v, void* y, float* l, float* m, int B,
                          unsigned long long* host_out) {
@@ -21,9 +23,8 @@ extern "C" int stamp_run(const void* q, const void* k, const void* v, void* y, f
     a.g.ws = 7; a.g.stride = 7; a.g.pad = 3;
     a.g.O[0] = 19; a.g.O[1] = 19; a.g.O[2] = 1; a.g.T = 49; a.g.L = 361; a.g.P = 128 * 128;
     a.d = 64; a.dv = 64; a.batch = B; a.scale = 0.125f;
-    const fa::WinDev g = fa::to_dev(a.g);
-    hipError_t e = fa::launch_rows1_dd<fa::bf16, 64, 64>(a, g, nullptr);
-    if (e != hipSuccess) return 1;
+    const char* why = nullptr;
+    if (fa::launch_windowed_fwd(a, nullptr, &why) != 0) return 1;
     if (hipDeviceSynchronize() != hipSuccess) return 2;
     if (hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_stamp_buf), sizeof(unsigned long long) * 8 * 361 * B) != hipSuccess) return 3;
     return 0;
@@ -42,7 +43,7 @@ extern "C" int stamp_run_bwd(const void* q, const void* k, const void* v, const 
     a.g.O[0] = 19; a.g.O[1] = 19; a.g.O[2] = 1; a.g.T = 49; a.g.L = 361; a.g.P = 128 * 128;
     a.d = 64; a.dv = 64; a.batch = B; a.scale = 0.125f;
     const char* why = nullptr;
-    if (fa::windowed_bwd_rows<fa::bf16>(a, nullptr, &why) != 0) return 1;
+    if (fa::launch_windowed_bwd(a, nullptr, &why) != 0) return 1;
     if (hipDeviceSynchronize() != hipSuccess) return 2;
     if (hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_stamp_buf), sizeof(unsigned long long) * 8 * 361 * B) != hipSuccess) return 3;
     return 0;
