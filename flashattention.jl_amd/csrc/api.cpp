@@ -14,6 +14,7 @@
 #include <string>
 
 #include "../../include/fa_hip.h"
+#include "fa_dense_plan.h"   // the dense plans (host functions)
 #include "fa_internal.h"
 #include "fa_windowed.h"   // the windowed plans (host functions; no kernel is instantiated here)
 
@@ -102,15 +103,17 @@ int fa_abi_version(void) { return FA_HIP_ABI_VERSION; }
 int fa_max_head_dim(void) { return fa::kMaxHeadDim; }
 
 // Not part of the public header: selects the forward kernel variant for A/B
-// benchmarking: 0 = auto (per head-dim class), 5 / 7 = 8 waves x {1, 2} query
-// blocks per wave on 32x32x16 MFMA; 20 = the default geometries with per-element Q
-// gathers and O stores; 30 = the one-wave-per-SIMD persistent kernel (fa_fwd_p4.hip)
-// where its shape rules allow.  (The measured-and-rejected 4-wave, 16x16x32 and
+// benchmarking, a fa::DenseFwdVariant (fa_dense_plan.h): 0 kFwdAuto (per head-dim class),
+// 5 kFwdW8B64 / 7 kFwdW8Q2 = 8 waves x {1, 2} query blocks per wave on 32x32x16 MFMA;
+// 20 kFwdNarrow = the default geometries with per-element Q gathers and O stores;
+// 30 kFwdP4 = the one-wave-per-SIMD persistent kernel (fa_fwd_p4.hip) where its shape
+// rules allow.  (The measured-and-rejected 4-wave, 16x16x32 and
 // 4-waves-per-SIMD geometries were removed in round 4, the persistent 8-wave d <= 64
 // kernel, a measured tie, in round 6; git history keeps them.)
 int fa_debug_set_fwd_variant(int v) {
     const int old = fa::g_fwd_variant;
-    if (v == 0 || v == 5 || v == 7 || v == 20 || v == 30) fa::g_fwd_variant = v;
+    if (v == fa::kFwdAuto || v == fa::kFwdW8B64 || v == fa::kFwdW8Q2 || v == fa::kFwdNarrow || v == fa::kFwdP4)
+        fa::g_fwd_variant = v;
     return old;
 }
 
@@ -134,19 +137,20 @@ int fa_debug_set_bwd_generic(int v) {
     return old;
 }
 
-// Not part of the public header: backward MFMA path (0 auto, 1 the dK/dV + dQ
-// passes, 2 the single pass wherever its shape conditions hold, 3 as 2 with the
-// hand-off's timeout word preset, which exercises the dQ fallback pass).  Builds with
-// -DFA_BWD_ABL also accept the timing-only ablations of the single pass, which compute
-// a WRONG dQ: 4, 5, 6 no waits, no running-sum traffic, neither; 7, 8 no running-sum
-// loads / stores; 9 no dS image writes; 10 no next-slice Q/dO DMA; 11 = 10 + 6.  Any other value is rejected (returns -1, the
-// mode is unchanged).
+// Not part of the public header: backward MFMA path, a fa::DenseBwdMode (fa_dense_plan.h):
+// 0 kBwdAuto, 1 kBwdTwoPass the dK/dV + dQ passes, 2 kBwdSinglePass the single pass wherever
+// its shape conditions hold, 3 kBwdSinglePassGiveUp as 2 with the hand-off's timeout word
+// preset, which exercises the dQ fallback pass.  Builds with -DFA_BWD_ABL also accept the
+// timing-only ablations of the single pass (kBwdAbl*), which compute a WRONG dQ: 4, 5, 6 no
+// waits, no running-sum traffic, neither; 7, 8 no running-sum loads / stores; 9 no dS image
+// writes; 10 no next-slice Q/dO DMA; 11 = 10 + 6.  Any other value is rejected (returns -1,
+// the mode is unchanged).
 int fa_debug_set_bwd_mode(int v) {
     const int old = fa::g_bwd_mode;
 #ifdef FA_BWD_ABL
-    constexpr int kMaxMode = 11;
+    constexpr int kMaxMode = fa::kBwdAblNoNextDmaNoWaitsNoSums;
 #else
-    constexpr int kMaxMode = 3;
+    constexpr int kMaxMode = fa::kBwdSinglePassGiveUp;
 #endif
     if (v < 0 || v > kMaxMode) return -1;
     fa::g_bwd_mode = v;
@@ -249,6 +253,49 @@ int fa_debug_win_bwd_plan(int dtype, int nspatial, const int64_t* spatial, int64
     if (!valid_dtype(dtype) || d < 1 || dv < 1 || batch < 1) return -1;
     if (make_geom(g, nspatial, spatial, ws, stride, pad, &why) != FA_OK) return -1;
     return fa::win_bwd_plan(dtype, g, d, dv, batch, mode, in_aligned16 != 0, grad_aligned16 != 0, fa::win_cus(cus));
+}
+
+// Not part of the public header (tests): the plan of a dense (causal != 0: causal) forward /
+// backward, fa::dense_fwd_plan / fa::dense_bwd_plan (fa_dense_plan.h).  Returns the kernel, a
+// fa::DenseFwdKernel / fa::DenseBwdKernel value (-1: invalid arguments, or a head dimension
+// above the compiled maximum), and writes the plan's other fields to out (may be null).
+// Every input is an argument, the knob values, the 16-B alignment facts, the workspace bytes
+// and the CU count included: nothing is read from the thread's knobs or the device.
+// forward out[17]: causal bits, pad, ldk, nsplit, tps, rows, nqb, total_wg, grid, block, wide,
+// off_k, off_v, off_opart, off_lpart, off_mpart, total.
+int fa_debug_dense_fwd_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, int causal,
+                            int variant, int causal_order, int kv_aligned16, int qo_aligned16, size_t ws_bytes,
+                            int cus, int64_t* out) {
+    if (!valid_dtype(dtype) || N < 1 || Nk < 1 || d < 1 || dv < 1 || batch < 1 || (causal && Nk < N)) return -1;
+    const fa::DenseFwdPlan pl = fa::dense_fwd_plan(dtype, N, Nk, d, dv, batch, causal != 0, {variant, causal_order},
+                                                   kv_aligned16 != 0, qo_aligned16 != 0, ws_bytes, cus);
+    if (out) {
+        const int64_t f[17] = {pl.causal, pl.pad, pl.ldk, pl.nsplit, pl.tps, pl.rows, pl.nqb, pl.total_wg, pl.grid,
+                               pl.block, pl.wide, (int64_t)pl.off_k, (int64_t)pl.off_v, (int64_t)pl.off_opart,
+                               (int64_t)pl.off_lpart, (int64_t)pl.off_mpart, (int64_t)pl.total};
+        for (int i = 0; i < 17; ++i) out[i] = f[i];
+    }
+    return pl.kernel;
+}
+// backward out[25]: padded, N, Nk, d, dv as run, slabs_fit, nkb, nqt, xcd, off_nD, off_nlse,
+// off_slab[10] (Q dQ K dK V dV O dO l m), off_flags, off_part, flag_bytes, total.
+int fa_debug_dense_bwd_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, int causal,
+                            int force_generic, int mode, int hoff, int xcd, int qkvdo_aligned16, size_t ws_bytes,
+                            int cus, int64_t* out) {
+    if (!valid_dtype(dtype) || N < 1 || Nk < 1 || d < 1 || dv < 1 || batch < 1 || (causal && Nk < N) ||
+        d > fa::kMaxHeadDim || dv > fa::kMaxHeadDim)
+        return -1;
+    const fa::DenseBwdPlan pl = fa::dense_bwd_plan(dtype, N, Nk, d, dv, batch, causal != 0,
+                                                   {force_generic, mode, hoff, xcd}, qkvdo_aligned16 != 0, ws_bytes, cus);
+    if (out) {
+        int64_t* o = out;
+        for (int64_t v : {(int64_t)pl.padded, pl.N, pl.Nk, pl.d, pl.dv, (int64_t)pl.slabs_fit, (int64_t)pl.nkb,
+                          (int64_t)pl.nqt, (int64_t)pl.xcd, (int64_t)pl.off_nD, (int64_t)pl.off_nlse})
+            *o++ = v;
+        for (size_t v : pl.off_slab) *o++ = (int64_t)v;
+        for (size_t v : {pl.off_flags, pl.off_part, pl.flag_bytes, pl.total}) *o++ = (int64_t)v;
+    }
+    return pl.kernel;
 }
 
 // Not part of the public header: workgroups of the persistent strip backward (0 = one per

@@ -23,6 +23,7 @@
 #include <utility>
 
 #include "fa_bwd_common.h"
+#include "fa_dense_plan.h"
 #include "fa_internal.h"
 #include "../../include/fa_hip.h"
 
@@ -33,28 +34,7 @@ namespace fa {
 // The boundary header states the same bound (tests/test_abi.py checks they agree).
 constexpr int kStallUs = FA_BWD_HANDOFF_STALL_US;
 
-// Single-pass hand-off words in the workspace (zeroed per call), in 32-bit words from
-// BwdParams::flags, for `batch` slabs of NS slices and KM members:
-struct FusedFlags {
-    int64_t cnt;    // [2 chains][batch][NS]: members of the chain that have published slice t
-    int64_t fin;    // [batch][NS]: tails of a wrapped slice's two chains that stored their sums
-    int64_t serr;   // [batch]: the slab gave up (its dQ is recomputed by bwd_dq_fast)
-    int64_t xcc;    // [batch][KM]: XCD of each member + 1 (L2-local hand-off)
-    int64_t prog;   // [batch][KM]: each member's count of publishes (plain stores, no contention)
-    int64_t garr;   // the launch's arrival count (one add per workgroup)
-    int64_t words;  // (a wrapped slice left to bwd_dq_fast's combine is flagged in hdr[3])
-};
-__host__ __device__ inline FusedFlags fused_flags(int64_t batch, int64_t NS, int64_t KM) {
-    FusedFlags f;
-    f.cnt = 0;
-    f.fin = 2 * batch * NS;
-    f.serr = 3 * batch * NS;
-    f.xcc = f.serr + batch;
-    f.prog = f.xcc + batch * KM;
-    f.garr = f.prog + batch * KM;
-    f.words = f.garr + 1;
-    return f;
-}
+// (the single pass's hand-off words, FusedFlags, are laid out in fa_dense_plan.h)
 
 struct BwdParams {
     const void *Q, *K, *V, *O, *dO;
@@ -92,7 +72,6 @@ struct BwdParams {
 };
 
 constexpr unsigned kBwdHdrMagic = 0x46414200u;   // "FAB\0"
-constexpr size_t kBwdHdrBytes = 256;
 
 // The pre-pass runs first on the stream in every 16/32-bit backward: its thread 0
 // (re)writes the workspace header, so the timeout word starts each call at hdr_err.
@@ -502,15 +481,13 @@ __global__ __launch_bounds__(256) void bwd_dq_f32(BwdParams p) {
 template <int D, int DV>
 static hipError_t launch_f32_dd(const BwdParams& p, hipStream_t s) {
     const int64_t nq = ((int64_t)p.N + 127) / 128 * p.batch, nk = ((int64_t)p.Nk + 127) / 128 * p.batch;
-    if (p.causal) {
-        hipLaunchKernelGGL((bwd_dq_f32<D, DV, true>), dim3((unsigned)nq), dim3(256), 0, s, p);
-        hipLaunchKernelGGL((bwd_dkdv_f32<D, DV, true>), dim3((unsigned)nk), dim3(256), 0, s, p);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL((bwd_dq_f32<D, DV>), dim3((unsigned)nq), dim3(256), 0, s, p);
-    hipLaunchKernelGGL((bwd_dkdv_f32<D, DV>), dim3((unsigned)nk), dim3(256), 0, s, p);
+    void (*dq)(BwdParams) = p.causal ? bwd_dq_f32<D, DV, true> : bwd_dq_f32<D, DV>;
+    void (*dkdv)(BwdParams) = p.causal ? bwd_dkdv_f32<D, DV, true> : bwd_dkdv_f32<D, DV>;
+    hipLaunchKernelGGL(dq, dim3((unsigned)nq), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(dkdv, dim3((unsigned)nk), dim3(256), 0, s, p);
     return hipGetLastError();
 }
+// (five class pairs, not nine: any d or dv above 64 runs the 128 x 128 kernels)
 static hipError_t launch_f32_mfma(const BwdParams& p, hipStream_t s) {
     if (p.d > 64 || p.dv > 64) return launch_f32_dd<128, 128>(p, s);
     const int Dc = p.d <= 32 ? 32 : 64, DVc = p.dv <= 32 ? 32 : 64;
@@ -1605,157 +1582,13 @@ extern "C" int fa_debug_bwd_stamps(unsigned long long* out, int n) {
 }
 #endif
 thread_local int g_bwd_force_generic = 0;   // benchmark knob
-thread_local int g_bwd_mode = 0;            // 0 auto, 1 split passes, 2 single pass where the shape allows
+thread_local int g_bwd_mode = kBwdAuto;     // a DenseBwdMode (fa_dense_plan.h)
 thread_local int g_bwd_l2local = -1;        // bwd_fused: L2-local hand-off when a slab sits on one XCD
                                             // (-1 auto: at d, dv <= 64; 0 never; 1 always)
 thread_local int g_bwd_hoff = 3;            // bwd_fused: step offset between consecutive members
 thread_local int g_bwd_stall_us = kStallUs; // bwd_fused: no-progress bound of a poll (us)
 thread_local int g_bwd_nodirect = 0;         // bwd_fused (tests): every wrapped slice left to bwd_dq_fast's combine
 thread_local int g_bwd_xcd = -1;            // bwd_fused: one XCD per slab where eligible (-1 auto, 0 never)
-
-template <class T, int D, int DV>
-static hipError_t launch_fast_dd(BwdParams p, hipStream_t s) {
-    if (p.causal) {   // always the two passes: no atomics, no hand-off
-        p.nblk = (p.N + 127) / 128;
-        p.total_wg = p.nblk * p.batch;
-        hipLaunchKernelGGL((bwd_dq_fast<T, D, DV, true>), dim3((unsigned)p.total_wg), dim3(256), 0, s, p);
-        p.nblk = (p.Nk + 127) / 128;
-        p.total_wg = p.nblk * p.batch;
-        hipLaunchKernelGGL((bwd_dkdv_fast<T, D, DV, true>), dim3((unsigned)p.total_wg), dim3(256), 0, s, p);
-        return hipGetLastError();
-    }
-    const bool fused = p.part != nullptr;
-    if (fused) {   // single pass; dQ pass below only after a hand-off timeout
-        p.total_wg = p.nkb * p.batch;
-        hipLaunchKernelGGL((bwd_fused<T, D, DV>), dim3((unsigned)p.total_wg), dim3(512), 0, s, p);
-        const FusedFlags ff = fused_flags(p.batch, p.nqt, p.nkb);
-        p.guard = p.err;
-        p.sguard = p.flags + ff.serr;
-        p.cguard = p.hdr + 3;
-        p.fin = p.flags + ff.fin;
-    }
-    p.nblk = (p.N + 127) / 128;
-    p.total_wg = p.nblk * p.batch;
-    hipLaunchKernelGGL((bwd_dq_fast<T, D, DV>), dim3((unsigned)p.total_wg), dim3(256), 0, s, p);
-    if (!fused) {
-        p.nblk = (p.Nk + 127) / 128;
-        p.total_wg = p.nblk * p.batch;
-        hipLaunchKernelGGL((bwd_dkdv_fast<T, D, DV>), dim3((unsigned)p.total_wg), dim3(256), 0, s, p);
-    }
-    return hipGetLastError();
-}
-template <class T, int D>
-static hipError_t launch_fast_d(const BwdParams& p, hipStream_t s) {
-    switch (p.dv) {
-        case 32: return launch_fast_dd<T, D, 32>(p, s);
-        case 64: return launch_fast_dd<T, D, 64>(p, s);
-        case 128: return launch_fast_dd<T, D, 128>(p, s);
-    }
-    return hipErrorInvalidValue;
-}
-template <class T>
-static hipError_t launch_fast(const BwdParams& p, hipStream_t s) {
-    switch (p.d) {
-        case 32: return launch_fast_d<T, 32>(p, s);
-        case 64: return launch_fast_d<T, 64>(p, s);
-        case 128: return launch_fast_d<T, 128>(p, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-// --------------------------------------------------------------------------
-// launcher
-// --------------------------------------------------------------------------
-// --------------------------------------------------------------------------
-// Padded fast path: 16-bit shapes the MFMA kernels do not take directly (N or
-// Nk not a multiple of 8, d or dv not 32 / 64 / 128) are copied into zero-padded
-// workspace slabs (N -> N8, Nk -> Nk8, d, dv -> their class) and run on the fast
-// kernels.  Zero keys and values are exact there: with the forward's lse they add
-// P·0 to dP and dS·0 to dQ, and their own dK / dV rows are dropped; padded
-// queries carry dO = O = 0 (so dS = 0) and l = 1, m = 0 (finite P, no NaN).
-// --------------------------------------------------------------------------
-static bool cls_dim(int64_t x) { return x == 32 || x == 64 || x == 128; }
-static bool shape_fast(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv) {
-    return dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_F64 && cls_dim(d) && cls_dim(dv) && N % 8 == 0 && Nk % 8 == 0 &&
-           N * d * 2 < INT32_MAX && Nk * d * 2 < INT32_MAX && N * dv * 2 < INT32_MAX && Nk * dv * 2 < INT32_MAX;
-}
-struct BwdPad {
-    bool on = false;
-    int64_t Np = 0, Nkp = 0, Dp = 0, DVp = 0;
-    size_t bytes = 0;
-};
-static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-static BwdPad pad_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    BwdPad pl;
-    if (dtype == FA_DTYPE_F32 || dtype == FA_DTYPE_F64 || d > kMaxHeadDim || dv > kMaxHeadDim ||
-        shape_fast(dtype, N, Nk, d, dv))
-        return pl;
-    pl.Np = (N + 7) / 8 * 8;
-    pl.Nkp = (Nk + 7) / 8 * 8;
-    pl.Dp = head_dim_class(d);
-    pl.DVp = head_dim_class(dv);
-    if (!shape_fast(dtype, pl.Np, pl.Nkp, pl.Dp, pl.DVp) || pl.Np * batch > INT32_MAX / 2 ||
-        pl.Nkp * batch > INT32_MAX / 2)
-        return pl;
-    pl.on = true;
-    const size_t q = al256((size_t)(pl.Np * pl.Dp * batch) * 2), k = al256((size_t)(pl.Nkp * pl.Dp * batch) * 2);
-    const size_t v = al256((size_t)(pl.Nkp * pl.DVp * batch) * 2), o = al256((size_t)(pl.Np * pl.DVp * batch) * 2);
-    const size_t lm = al256((size_t)(pl.Np * batch) * 4);
-    pl.bytes = 2 * q + 2 * k + 2 * v + 2 * o + 2 * lm;   // Q dQ, K dK, V dV, O dO, l m
-    return pl;
-}
-
-// Single-pass plan (bwd_fused) on the shape the fast kernels run (padded or not):
-// K = ceil(Nk/256) members per slab, T = ceil(N/64) slices, step offset 3 (needs
-// 3K <= T); K <= CUs, one XCD per slab when K <= CUs/8 and the slab count is a
-// multiple of 8 (a slab's members then run together: speed, not correctness, which
-// needs no co-residency); auto only when the grid fills the chip once.  Workspace: the hand-off words (FusedFlags), then the two chains'
-// running fp32 dQ sums (2 x 4·N·d bytes per slab).
-struct FusedPlan {
-    bool on = false;
-    int nkb = 0, nqt = 0, xcd = 0;
-    size_t flag_bytes = 0, bytes = 0;
-};
-static FusedPlan fused_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch,
-                            hipStream_t s = nullptr) {
-    FusedPlan f;
-    if (dtype == FA_DTYPE_F32 || dtype == FA_DTYPE_F64 || g_bwd_mode == 1 || g_bwd_force_generic || !shape_fast(dtype, N, Nk, d, dv)) return f;
-    const int64_t K = (Nk + 255) / 256, T = (N + 63) / 64;
-    const int cus = device_cus(s);
-    if (cus < 8 || g_bwd_hoff * K > T || K > cus || batch * K > INT32_MAX / 2 || 2 * T * (d / 16) * 4096 >= INT32_MAX ||
-        T >= (1 << 20))   // a slice index fits the 20 bits bwd_fused packs it in
-        return f;
-    const int xcd = (K <= cus / 8 && batch % 8 == 0 && g_bwd_xcd != 0) ? 1 : 0;
-    if (g_bwd_mode == 0) {
-        // auto: the grid fills the chip, and K divides the CUs a slab's members are dealt
-        // over (one XCD's, or the chip's), so no slab waits part-resident behind another
-        if (batch * K < cus || (xcd ? cus / 8 : cus) % K != 0) return f;
-    }
-    f.on = true;
-    f.nkb = (int)K;
-    f.nqt = (int)T;
-    f.xcd = xcd;
-    f.flag_bytes = al256((size_t)fused_flags(batch, T, K).words * 4);   // FusedFlags
-    f.bytes = f.flag_bytes + al256((size_t)(2 * batch * T * (d / 16)) * 4096) + 256;   // two chains' running sums
-    return f;
-}
-
-size_t dense_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    if (dtype == FA_DTYPE_F64) return kBwdHdrBytes + (size_t)(2 * N * batch * sizeof(double) + 256);   // nD, nlse in double
-    const BwdPad pl = pad_plan(dtype, N, Nk, d, dv, batch);
-    const int64_t rows = pl.on ? pl.Np : N;
-    const FusedPlan fz = pl.on ? fused_plan(dtype, pl.Np, pl.Nkp, pl.Dp, pl.DVp, batch)
-                               : fused_plan(dtype, N, Nk, d, dv, batch);
-    return kBwdHdrBytes + (size_t)(2 * rows * batch * sizeof(float) + 256) + (pl.on ? pl.bytes + 256 : 0) + fz.bytes;
-}
-
-// fa_causal_bwd: header, row statistics, pad plan; never the single pass's running sums
-size_t causal_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    if (dtype == FA_DTYPE_F64) return kBwdHdrBytes + (size_t)(2 * N * batch * sizeof(double) + 256);
-    const BwdPad pl = pad_plan(dtype, N, Nk, d, dv, batch);
-    const int64_t rows = pl.on ? pl.Np : N;
-    return kBwdHdrBytes + (size_t)(2 * rows * batch * sizeof(float) + 256) + (pl.on ? pl.bytes + 256 : 0);
-}
 
 // dst (Np, Cp, B) <- src (N, C, B), zero-filled
 template <class T>
@@ -1792,6 +1625,11 @@ __global__ __launch_bounds__(256) void bwd_pad_lm(const float* __restrict__ l, c
     lp[e] = n < N ? l[b * N + n] : 1.0f;
     mp[e] = n < N ? m[b * N + n] : 0.0f;
 }
+
+// --------------------------------------------------------------------------
+// launcher: dense_bwd_plan (fa_dense_plan.h) names the kernel, the extents it runs on
+// and the workspace offsets; nothing below decides any of them again
+// --------------------------------------------------------------------------
 template <class T>
 static hipError_t pad_launch(const void* src, void* dst, int64_t N, int64_t C, int64_t Np, int64_t Cp, int64_t B,
                              hipStream_t s) {
@@ -1809,6 +1647,39 @@ static hipError_t unpad_launch(const void* src, void* dst, int64_t N, int64_t C,
     return hipGetLastError();
 }
 
+// kDenseBwdTwoPass / kDenseBwdSinglePass at (d, dv) = (D, DV)
+template <class T, int D, int DV>
+static hipError_t launch_fast_dd(const DenseBwdPlan& pl, BwdParams p, hipStream_t s) {
+    // a pass of 128-row blocks over `rows`
+    auto pass = [&](void (*kernel)(BwdParams), int rows) {
+        p.nblk = (rows + 127) / 128;
+        p.total_wg = p.nblk * p.batch;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)p.total_wg), dim3(256), 0, s, p);
+    };
+    const bool single = pl.kernel == kDenseBwdSinglePass;
+    if (single) {   // dQ pass below only after a hand-off timeout
+        p.total_wg = p.nkb * p.batch;
+        hipLaunchKernelGGL((bwd_fused<T, D, DV>), dim3((unsigned)p.total_wg), dim3(512), 0, s, p);
+        const FusedFlags ff = fused_flags(p.batch, p.nqt, p.nkb);
+        p.guard = p.err;
+        p.sguard = p.flags + ff.serr;
+        p.cguard = p.hdr + 3;
+        p.fin = p.flags + ff.fin;
+    }
+    // (causal: always the two passes: no atomics, no hand-off)
+    pass(p.causal ? bwd_dq_fast<T, D, DV, true> : bwd_dq_fast<T, D, DV>, p.N);
+    if (!single) pass(p.causal ? bwd_dkdv_fast<T, D, DV, true> : bwd_dkdv_fast<T, D, DV>, p.Nk);
+    return hipGetLastError();
+}
+template <class T>
+static hipError_t launch_fast(const DenseBwdPlan& pl, const BwdParams& p, hipStream_t s) {
+    hipError_t e = hipErrorInvalidValue;
+    by_dim_class(p.d, [&](auto D) {
+        by_dim_class(p.dv, [&](auto DV) { e = launch_fast_dd<T, decltype(D)::value, decltype(DV)::value>(pl, p, s); });
+    });
+    return e;
+}
+
 template <class T, class A = float>
 static hipError_t launch_generic(const BwdParams& p, hipStream_t s) {
     const int64_t nq = ((int64_t)p.N + kGT - 1) / kGT * p.batch;
@@ -1816,78 +1687,83 @@ static hipError_t launch_generic(const BwdParams& p, hipStream_t s) {
     const size_t rows = kGT * (2 * (p.d + 1) + 2 * (p.dv + 1));
     const size_t sm_dq = sizeof(A) * (rows + kGT * (kGT + 1));
     const size_t sm_kv = sizeof(A) * (rows + 2 * kGT * (kGT + 1));
+    void (*dq)(BwdParams) = p.causal ? bwd_generic_dq<T, A, true> : bwd_generic_dq<T, A>;
+    void (*dkdv)(BwdParams) = p.causal ? bwd_generic_dkdv<T, A, true> : bwd_generic_dkdv<T, A>;
     // > 64 KiB of dynamic LDS at d = dv = 128 (gfx950 has 160 KiB per CU)
-    if (p.causal) {
-        (void)hipFuncSetAttribute((const void*)bwd_generic_dq<T, A, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_dq);
-        (void)hipFuncSetAttribute((const void*)bwd_generic_dkdv<T, A, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_kv);
-        hipLaunchKernelGGL((bwd_generic_dq<T, A, true>), dim3((unsigned)nq), dim3(kGThreads), sm_dq, s, p);
-        hipLaunchKernelGGL((bwd_generic_dkdv<T, A, true>), dim3((unsigned)nk), dim3(kGThreads), sm_kv, s, p);
-        return hipGetLastError();
-    }
-    (void)hipFuncSetAttribute((const void*)bwd_generic_dq<T, A>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_dq);
-    (void)hipFuncSetAttribute((const void*)bwd_generic_dkdv<T, A>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_kv);
-    hipLaunchKernelGGL((bwd_generic_dq<T, A>), dim3((unsigned)nq), dim3(kGThreads), sm_dq, s, p);
-    hipLaunchKernelGGL((bwd_generic_dkdv<T, A>), dim3((unsigned)nk), dim3(kGThreads), sm_kv, s, p);
+    (void)hipFuncSetAttribute((const void*)dq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_dq);
+    (void)hipFuncSetAttribute((const void*)dkdv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_kv);
+    hipLaunchKernelGGL(dq, dim3((unsigned)nq), dim3(kGThreads), sm_dq, s, p);
+    hipLaunchKernelGGL(dkdv, dim3((unsigned)nk), dim3(kGThreads), sm_kv, s, p);
     return hipGetLastError();
 }
 
+// the pre-pass, then the plan's kernel
 template <class T>
-static hipError_t launch_typed(const BwdParams& p, hipStream_t s, bool fast) {
+static hipError_t launch_typed(const DenseBwdPlan& pl, const BwdParams& p, hipStream_t s) {
     const int64_t total = (int64_t)p.N * p.batch;
     bool vec = false;
     if constexpr (sizeof(T) == 2) {
-        vec = p.N % 8 == 0 && ((uintptr_t)p.O & 15u) == 0 && ((uintptr_t)p.dO & 15u) == 0;
+        vec = p.N % 8 == 0 && aligned16(p.O) && aligned16(p.dO);
         if (vec) hipLaunchKernelGGL(bwd_prepass_v<T>, dim3((unsigned)((total / 8 + 255) / 256)), dim3(256), 0, s, p);
     }
     if (!vec) hipLaunchKernelGGL(bwd_prepass<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if constexpr (!std::is_same<T, float>::value) {
-        if (fast) return launch_fast<T>(p, s);
+    if constexpr (std::is_same<T, float>::value) {
+        if (pl.kernel == kDenseBwdF32Mfma) return launch_f32_mfma(p, s);
     } else {
-        if (fast) return launch_f32_mfma(p, s);
+        if (pl.kernel == kDenseBwdTwoPass || pl.kernel == kDenseBwdSinglePass) return launch_fast<T>(pl, p, s);
     }
     return launch_generic<T>(p, s);
 }
 
-static bool aligned16(const void* ptr) { return ((uintptr_t)ptr & 15u) == 0; }
+static DenseBwdKnobs bwd_knobs() { return {g_bwd_force_generic, g_bwd_mode, g_bwd_hoff, g_bwd_xcd}; }
 
-// Single-pass state in the workspace at w: per-slice counters (zeroed here), then the
-// running dQ sums.  The status word is hdr[1], which the pre-pass sets to hdr_err.
-static hipError_t fused_setup(BwdParams& p, const FusedPlan& fz, char* w, hipStream_t s) {
-    p.flags = (unsigned*)w;
-    p.part = (float*)(w + fz.flag_bytes);
-    p.nkb = fz.nkb; p.nqt = fz.nqt; p.xcd = fz.xcd;
+// The shape's own needs under the thread's knobs on the current device: aligned tensors, room
+// for everything (the queries have no pointers).
+size_t dense_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
+    return dense_bwd_plan(dtype, N, Nk, d, dv, batch, false, bwd_knobs(), true, SIZE_MAX, device_cus(nullptr)).total;
+}
+// fa_causal_bwd: header, row statistics, padded slabs; never the single pass's part (and so no device query)
+size_t causal_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
+    return dense_bwd_plan(dtype, N, Nk, d, dv, batch, true, bwd_knobs(), true, SIZE_MAX, 0).total;
+}
+
+// Single-pass state in the workspace: per-slice counters (zeroed here), then the running dQ
+// sums.  The status word is hdr[1], which the pre-pass sets to hdr_err.
+static hipError_t fused_setup(BwdParams& p, const DenseBwdPlan& pl, int mode, char* w, hipStream_t s) {
+    p.flags = (unsigned*)(w + pl.off_flags);
+    p.part = (float*)(w + pl.off_part);
+    p.nkb = pl.nkb; p.nqt = pl.nqt; p.xcd = pl.xcd;
     p.hdr_plan = 1;
-    // mode 3 (tests): the timeout word starts set, so every poll gives up and the
-    // guarded dQ pass must recompute dQ of every slab
-    p.hdr_err = g_bwd_mode == 3 ? 1u : 0u;
+    // kBwdSinglePassGiveUp (tests): the timeout word starts set, so every poll gives up and
+    // the guarded dQ pass must recompute dQ of every slab
+    p.hdr_err = mode == kBwdSinglePassGiveUp ? 1u : 0u;
     // L2-local hand-off: +6 % at d = dv = 64, -1 % at 128, where a slice's running
     // sums (32 KB) in flight over three steps fill most of the 4-MB L2 that also
     // serves the slab's Q / dO (profiles/r04_bwd_handoff_modes.log)
-    p.l2local = g_bwd_l2local >= 0 ? g_bwd_l2local : (p.d <= 64 && p.dv <= 64 ? 1 : 0);
+    p.l2local = g_bwd_l2local >= 0 ? g_bwd_l2local : (pl.d <= 64 && pl.dv <= 64 ? 1 : 0);
     p.hoff = g_bwd_hoff;
     p.stall_ticks = g_bwd_stall_us * 100;
     p.nodirect = g_bwd_nodirect;
 #ifdef FA_BWD_ABL
-    p.ablate = g_bwd_mode == 7 ? 8 : g_bwd_mode == 8 ? 16 : g_bwd_mode == 9 ? 32 : g_bwd_mode == 10 ? 64
-             : g_bwd_mode == 11 ? 64 | 3 : g_bwd_mode >= 4 ? g_bwd_mode - 3 : 0;
+    p.ablate = bwd_ablate_bits(mode);
 #endif
-    hipError_t e = hipMemsetAsync(w, 0, fz.flag_bytes, s);
-    if (e == hipSuccess && g_bwd_mode == 3)
-        e = hipMemsetD32Async((hipDeviceptr_t)(p.flags + fused_flags(p.batch, fz.nqt, fz.nkb).serr), 1u, (size_t)p.batch, s);
+    hipError_t e = hipMemsetAsync(p.flags, 0, pl.flag_bytes, s);
+    if (e == hipSuccess && mode == kBwdSinglePassGiveUp)
+        e = hipMemsetD32Async((hipDeviceptr_t)(p.flags + fused_flags(p.batch, pl.nqt, pl.nkb).serr), 1u, (size_t)p.batch, s);
     return e;
 }
 
 int dense_bwd_handoff_status(const void* workspace, size_t workspace_bytes, hipStream_t s, int* status,
                              const char** why) {
-    const uintptr_t ws0 = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-    if (!workspace || ws0 + 8 > (uintptr_t)workspace + workspace_bytes) {
+    const char* const hdr = al256((void*)workspace) + DenseBwdPlan{}.off_hdr;
+    if (!workspace || (uintptr_t)hdr + 8 > (uintptr_t)workspace + workspace_bytes) {
         *why = "workspace missing or smaller than its header";
         return FA_ERR_INVALID_ARG;
     }
     unsigned h[2] = {0u, 0u};
-    hipError_t e = hipMemcpyAsync(h, (const void*)ws0, sizeof(h), hipMemcpyDeviceToHost, s);
+    hipError_t e = hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) {
         *why = hipGetErrorString(e);
@@ -1915,8 +1791,16 @@ int launch_dense_bwd(const DenseBwdArgs& a, hipStream_t s, const char** why) {
         *why = "extent exceeds 2^31 elements";
         return FA_ERR_UNSUPPORTED;
     }
-    if (a.causal && a.workspace_bytes < causal_bwd_workspace(a.dtype, a.N, a.Nk, a.d, a.dv, a.batch)) {
-        *why = "workspace smaller than fa_causal_bwd_workspace()";
+    const DenseBwdKnobs kn = bwd_knobs();
+    char* const w = al256(a.workspace);
+    const size_t slack = (size_t)(w - (char*)a.workspace);
+    const DenseBwdPlan pl = dense_bwd_plan(a.dtype, a.N, a.Nk, a.d, a.dv, a.batch, a.causal != 0, kn,
+                                           aligned16(a.Q) && aligned16(a.K) && aligned16(a.V) && aligned16(a.dO),
+                                           a.workspace_bytes > slack ? a.workspace_bytes - slack : 0, device_cus(s));
+    // causal and Float64 totals depend on the shape alone: the whole of it must be there.
+    // (A padded call checks its slabs below; the single pass's part is optional.)
+    if ((a.causal || a.dtype == FA_DTYPE_F64) && a.workspace_bytes < pl.total) {
+        *why = a.causal ? "workspace smaller than fa_causal_bwd_workspace()" : "workspace smaller than fa_dense_bwd_workspace()";
         return FA_ERR_WORKSPACE;
     }
     BwdParams p;
@@ -1924,25 +1808,17 @@ int launch_dense_bwd(const DenseBwdArgs& a, hipStream_t s, const char** why) {
     p.off = a.causal ? (int)(a.Nk - a.N) : 0;   // from the caller's extents, also on the padded path
     p.Q = a.Q; p.K = a.K; p.V = a.V; p.O = a.O; p.dO = a.dO; p.l = a.l; p.m = a.m;
     p.dQ = a.dQ; p.dK = a.dK; p.dV = a.dV;
-    const uintptr_t ws0 = ((uintptr_t)a.workspace + 255) & ~(uintptr_t)255;
-    p.hdr = (unsigned*)ws0;
+    p.hdr = (unsigned*)(w + pl.off_hdr);
     p.err = p.hdr + 1;
-    const uintptr_t ws = ws0 + kBwdHdrBytes;
-    p.nD = (float*)ws;
-    p.nlse = p.nD + a.N * a.batch;
+    p.nD = (float*)(w + pl.off_nD);
+    p.nlse = (float*)(w + pl.off_nlse);
     p.N = (int)a.N; p.Nk = (int)a.Nk; p.d = (int)a.d; p.dv = (int)a.dv; p.batch = (int)a.batch;
     p.scale = a.scale;
     p.scale_log2 = a.scale * kLog2e;
     hipError_t e;
-    if (a.dtype == FA_DTYPE_F64) {
+    if (pl.kernel == kDenseBwdF64) {
         // Float64: row statistics recomputed in double (not from the float32 l, m),
-        // then the SIMT passes in double
-        if (!a.causal && a.workspace_bytes < dense_bwd_workspace(a.dtype, a.N, a.Nk, a.d, a.dv, a.batch)) {
-            *why = "workspace smaller than fa_dense_bwd_workspace()";
-            return FA_ERR_WORKSPACE;
-        }
-        double* nD = (double*)ws;
-        double* nlse = nD + a.N * a.batch;
+        // then the SIMT passes in double.
         // plan 0; word 3 (a chain-B tail left its slice to the combine) belongs to the
         // current call like word 0, so it is cleared wherever word 0 is written; word 2
         // (the sticky give-up count) is left alone
@@ -1951,10 +1827,8 @@ int launch_dense_bwd(const DenseBwdArgs& a, hipStream_t s, const char** why) {
             *why = hipGetErrorString(e);
             return FA_ERR_HIP;
         }
-        p.nD = (float*)nD;
-        p.nlse = (float*)nlse;
         p.scale64 = a.scale64 > 0.0 ? a.scale64 : (double)a.scale;
-        const int rc = launch_f64_bwd_stats(a, nD, nlse, s, why);
+        const int rc = launch_f64_bwd_stats(a, (double*)p.nD, (double*)p.nlse, s, why);
         if (rc != FA_OK) return rc;
         if ((e = launch_generic<double, double>(p, s)) != hipSuccess) {   // (causal: its CAUSAL instantiations)
             *why = hipGetErrorString(e);
@@ -1962,84 +1836,51 @@ int launch_dense_bwd(const DenseBwdArgs& a, hipStream_t s, const char** why) {
         }
         return FA_OK;
     }
-    const bool fast = !g_bwd_force_generic && shape_fast(a.dtype, a.N, a.Nk, a.d, a.dv) &&
-                      aligned16(a.Q) && aligned16(a.K) && aligned16(a.V) && aligned16(a.dO);
-    const BwdPad pl = pad_plan(a.dtype, a.N, a.Nk, a.d, a.dv, a.batch);
-    if (!fast && pl.on && !g_bwd_force_generic) {
-        // padded fast path: workspace = [nD | nlse] (Np rows) then the padded slabs
+    if (pl.padded && !pl.slabs_fit) {
+        *why = "workspace smaller than fa_dense_bwd_workspace()";
+        return FA_ERR_WORKSPACE;
+    }
+    if (pl.kernel == kDenseBwdSinglePass && (e = fused_setup(p, pl, kn.mode, w, s)) != hipSuccess) {
+        *why = hipGetErrorString(e);
+        return FA_ERR_HIP;
+    }
+    if (pl.padded) {
+        // the kernels run on zero-padded copies in the workspace slabs; dQ, dK, dV are copied back
         const int64_t B = a.batch;
-        char* w = (char*)(ws + al256((size_t)(2 * pl.Np * B) * sizeof(float)));
-        auto take = [&](size_t bytes) { void* q = w; w += al256(bytes); return q; };
-        void* Qp = take((size_t)(pl.Np * pl.Dp * B) * 2);
-        void* dQp = take((size_t)(pl.Np * pl.Dp * B) * 2);
-        void* Kp = take((size_t)(pl.Nkp * pl.Dp * B) * 2);
-        void* dKp = take((size_t)(pl.Nkp * pl.Dp * B) * 2);
-        void* Vp = take((size_t)(pl.Nkp * pl.DVp * B) * 2);
-        void* dVp = take((size_t)(pl.Nkp * pl.DVp * B) * 2);
-        void* Op = take((size_t)(pl.Np * pl.DVp * B) * 2);
-        void* dOp = take((size_t)(pl.Np * pl.DVp * B) * 2);
-        float* lp = (float*)take((size_t)(pl.Np * B) * 4);
-        float* mp = (float*)take((size_t)(pl.Np * B) * 4);
-        if ((size_t)(w - (char*)a.workspace) > a.workspace_bytes) {
-            *why = "workspace smaller than fa_dense_bwd_workspace()";
-            return FA_ERR_WORKSPACE;
-        }
-        const FusedPlan fz = a.causal ? FusedPlan{} : fused_plan(a.dtype, pl.Np, pl.Nkp, pl.Dp, pl.DVp, B, s);
-        if (fz.on && (size_t)(w - (char*)a.workspace) + fz.bytes <= a.workspace_bytes &&
-            (e = fused_setup(p, fz, w, s)) != hipSuccess) {
-            *why = hipGetErrorString(e);
-            return FA_ERR_HIP;
-        }
         const bool half = a.dtype == FA_DTYPE_F16;
-        auto pad = [&](const void* src, void* dst, int64_t N, int64_t C, int64_t Np, int64_t Cp) {
-            return half ? pad_launch<f16>(src, dst, N, C, Np, Cp, B, s) : pad_launch<bf16>(src, dst, N, C, Np, Cp, B, s);
+        auto slab = [&](BwdSlab i) { return (void*)(w + pl.off_slab[i]); };
+        auto pad = [&](const void* src, BwdSlab dst, int64_t N, int64_t C, int64_t Np, int64_t Cp) {
+            return half ? pad_launch<f16>(src, slab(dst), N, C, Np, Cp, B, s) : pad_launch<bf16>(src, slab(dst), N, C, Np, Cp, B, s);
         };
-        auto unpad = [&](const void* src, void* dst, int64_t N, int64_t C, int64_t Np, int64_t Cp) {
-            return half ? unpad_launch<f16>(src, dst, N, C, Np, Cp, B, s) : unpad_launch<bf16>(src, dst, N, C, Np, Cp, B, s);
+        auto unpad = [&](BwdSlab src, void* dst, int64_t N, int64_t C, int64_t Np, int64_t Cp) {
+            return half ? unpad_launch<f16>(slab(src), dst, N, C, Np, Cp, B, s) : unpad_launch<bf16>(slab(src), dst, N, C, Np, Cp, B, s);
         };
-        const int64_t tlm = pl.Np * B;
-        if ((e = pad(a.Q, Qp, a.N, a.d, pl.Np, pl.Dp)) != hipSuccess ||
-            (e = pad(a.K, Kp, a.Nk, a.d, pl.Nkp, pl.Dp)) != hipSuccess ||
-            (e = pad(a.V, Vp, a.Nk, a.dv, pl.Nkp, pl.DVp)) != hipSuccess ||
-            (e = pad(a.O, Op, a.N, a.dv, pl.Np, pl.DVp)) != hipSuccess ||
-            (e = pad(a.dO, dOp, a.N, a.dv, pl.Np, pl.DVp)) != hipSuccess) {
+        const int64_t tlm = pl.N * B;
+        if ((e = pad(a.Q, kSlabQ, a.N, a.d, pl.N, pl.d)) != hipSuccess ||
+            (e = pad(a.K, kSlabK, a.Nk, a.d, pl.Nk, pl.d)) != hipSuccess ||
+            (e = pad(a.V, kSlabV, a.Nk, a.dv, pl.Nk, pl.dv)) != hipSuccess ||
+            (e = pad(a.O, kSlabO, a.N, a.dv, pl.N, pl.dv)) != hipSuccess ||
+            (e = pad(a.dO, kSlabDO, a.N, a.dv, pl.N, pl.dv)) != hipSuccess) {
             *why = hipGetErrorString(e);
             return FA_ERR_HIP;
         }
-        hipLaunchKernelGGL(bwd_pad_lm, dim3((unsigned)((tlm + 255) / 256)), dim3(256), 0, s, a.l, a.m, lp, mp,
-                           (int)a.N, (int)pl.Np, tlm);
-        BwdParams q = p;
-        q.Q = Qp; q.K = Kp; q.V = Vp; q.O = Op; q.dO = dOp; q.l = lp; q.m = mp;
-        q.dQ = dQp; q.dK = dKp; q.dV = dVp;
-        q.nlse = q.nD + pl.Np * B;
-        q.N = (int)pl.Np; q.Nk = (int)pl.Nkp; q.d = (int)pl.Dp; q.dv = (int)pl.DVp;
-        e = half ? launch_typed<f16>(q, s, true) : launch_typed<bf16>(q, s, true);
-        if (e == hipSuccess && (e = unpad(dQp, a.dQ, a.N, a.d, pl.Np, pl.Dp)) == hipSuccess &&
-            (e = unpad(dKp, a.dK, a.Nk, a.d, pl.Nkp, pl.Dp)) == hipSuccess)
-            e = unpad(dVp, a.dV, a.Nk, a.dv, pl.Nkp, pl.DVp);
-        if (e != hipSuccess) {
-            *why = hipGetErrorString(e);
-            return FA_ERR_HIP;
+        hipLaunchKernelGGL(bwd_pad_lm, dim3((unsigned)((tlm + 255) / 256)), dim3(256), 0, s, a.l, a.m,
+                           (float*)slab(kSlabL), (float*)slab(kSlabM), (int)a.N, (int)pl.N, tlm);
+        p.Q = slab(kSlabQ); p.K = slab(kSlabK); p.V = slab(kSlabV); p.O = slab(kSlabO); p.dO = slab(kSlabDO);
+        p.l = (const float*)slab(kSlabL); p.m = (const float*)slab(kSlabM);
+        p.dQ = slab(kSlabDQ); p.dK = slab(kSlabDK); p.dV = slab(kSlabDV);
+        p.N = (int)pl.N; p.Nk = (int)pl.Nk; p.d = (int)pl.d; p.dv = (int)pl.dv;
+        e = half ? launch_typed<f16>(pl, p, s) : launch_typed<bf16>(pl, p, s);
+        if (e == hipSuccess && (e = unpad(kSlabDQ, a.dQ, a.N, a.d, pl.N, pl.d)) == hipSuccess &&
+            (e = unpad(kSlabDK, a.dK, a.Nk, a.d, pl.Nk, pl.d)) == hipSuccess)
+            e = unpad(kSlabDV, a.dV, a.Nk, a.dv, pl.Nk, pl.dv);
+    } else {
+        switch (a.dtype) {
+            case FA_DTYPE_BF16: e = launch_typed<bf16>(pl, p, s); break;
+            case FA_DTYPE_F16: e = launch_typed<f16>(pl, p, s); break;
+            case FA_DTYPE_F32: e = launch_typed<float>(pl, p, s); break;
+            default: *why = "unknown dtype"; return FA_ERR_INVALID_ARG;
         }
-        return FA_OK;
-    }
-    if (fast && !a.causal) {   // causal never takes the single pass (fa_hip.h: fa_causal_bwd)
-        const FusedPlan fz = fused_plan(a.dtype, a.N, a.Nk, a.d, a.dv, a.batch, s);
-        char* w = (char*)ws + al256((size_t)(2 * a.N * a.batch) * sizeof(float));
-        if (fz.on && (size_t)(w - (char*)a.workspace) + fz.bytes <= a.workspace_bytes &&
-            (e = fused_setup(p, fz, w, s)) != hipSuccess) {
-            *why = hipGetErrorString(e);
-            return FA_ERR_HIP;
-        }
-    }
-    switch (a.dtype) {
-        case FA_DTYPE_BF16: e = launch_typed<bf16>(p, s, fast); break;
-        case FA_DTYPE_F16: e = launch_typed<f16>(p, s, fast); break;
-        case FA_DTYPE_F32:   // fp32 MFMA kernels (exact fp32 products)
-            e = launch_typed<float>(p, s, !g_bwd_force_generic &&
-                                              a.N * a.batch < INT32_MAX / 2 && a.Nk * a.batch < INT32_MAX / 2);
-            break;
-        default: *why = "unknown dtype"; return FA_ERR_INVALID_ARG;
     }
     if (e != hipSuccess) {
         *why = hipGetErrorString(e);

@@ -44,6 +44,7 @@
 
 #include "fa_common.h"
 #include "fa_internal.h"
+#include "fa_dense_plan.h"
 #include "fa_fwd_params.h"
 #include "../../include/fa_hip.h"
 
@@ -64,8 +65,8 @@
 
 namespace fa {
 
-thread_local int g_fwd_variant = 0;
-thread_local int g_fwd_last_path = 0;   // fa_debug_fwd_last_path: 30 when the last fast launch ran fa_fwd_p4  // 0: auto; 4..7: forced geometry (benchmark knob, fa_debug_set_fwd_variant)
+thread_local int g_fwd_variant = kFwdAuto;   // a DenseFwdVariant (fa_dense_plan.h): benchmark knob, fa_debug_set_fwd_variant
+thread_local int g_fwd_last_path = 0;   // fa_debug_fwd_last_path: 30 when the last fast launch ran fa_fwd_p4
 thread_local float g_fwd_rescale_log2 = kRescaleLog2;  // fa_debug_set_rescale_threshold (accuracy tests)
 thread_local int g_causal_rev = 2;   // causal fast forward: launch order of the query blocks (fa_debug_set_causal_order)
 
@@ -1015,204 +1016,6 @@ __global__ __launch_bounds__(256) void fwd_split_combine(FwdParams p, int64_t to
     }
 }
 
-// Split-KV plan for the fast kernels: grids of fewer workgroups than CUs split the
-// key range so that ~512 workgroups run (each at least 2 tiles of 64 keys).
-struct SplitPlan {
-    int nsplit = 1, tps = 0;
-    size_t bytes = 0;
-};
-static SplitPlan split_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    SplitPlan sp;
-    const int Dc = head_dim_class(d), DVc = head_dim_class(dv);
-    if (dtype == FA_DTYPE_F32 || dtype == FA_DTYPE_F64 || !Dc || !DVc) return sp;
-    const int64_t rows = (Dc <= 64 && DVc <= 64) ? 512 : 256;
-    const int64_t wgs = (N + rows - 1) / rows * batch;
-    const int64_t NT = (Nk + kBN - 1) / kBN;
-    if (wgs >= 256 || NT < 4) return sp;
-    int64_t ns = std::min<int64_t>((512 + wgs - 1) / wgs, NT / 2);
-    if (ns < 2) return sp;
-    const int64_t tps = (NT + ns - 1) / ns;
-    ns = (NT + tps - 1) / tps;
-    if (ns < 2 || ns * wgs > INT32_MAX) return sp;
-    sp.nsplit = (int)ns;
-    sp.tps = (int)tps;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    sp.bytes = al((size_t)(ns * batch * N * dv) * 4) + 2 * al((size_t)(ns * batch * N) * 4) + 256;
-    return sp;
-}
-
-// --------------------------------------------------------------------------
-// launcher
-// --------------------------------------------------------------------------
-bool launch_dense_fwd_p4(const FwdParams& p, int Dc, int DVc, int dtype, hipStream_t s, hipError_t* err);
-
-template <class T, int D>
-static hipError_t launch_dv(const FwdParams& p, int DVc, dim3 grid, hipStream_t s) {
-    // one wave per SIMD, persistent (fa_fwd_p4.hip): the default at d = dv = 128 (5-8 %
-    // over the 8-wave kernel, bitwise equal: profiles/r04_fwd_p4_default_d128_ab.log);
-    // at 64 the 8-wave kernel stays (p4 is 15 % slower there); variant 30 forces it
-    if (p.causal) {
-        // causal: the default geometry of the head-dim class (fast), else the generic kernel;
-        // fa_debug_set_fwd_variant does not apply
-        if (p.fast) {
-            const bool q2 = D <= 64 && DVc <= 64;
-            FwdParams q = p;
-            q.nqb = (q.N + (q2 ? 512 : 256) - 1) / (q2 ? 512 : 256);
-            q.total_wg = q.nqb * q.batch;
-            // order 2 needs every XCD's share of the grid to hold whole slabs
-            if (g_causal_rev == 2 && q.total_wg % 8 == 0 && (q.total_wg / 8) % q.nqb == 0) q.causal = 1 | 4;
-            const dim3 g2((unsigned)q.total_wg), blk(512);
-#define FA_LAUNCH_C(KER)                                                                \
-            switch (DVc) {                                                              \
-                case 32: hipLaunchKernelGGL((KER<T, D, 32>), g2, blk, 0, s, q); break;  \
-                case 64: hipLaunchKernelGGL((KER<T, D, 64>), g2, blk, 0, s, q); break;  \
-                case 128: hipLaunchKernelGGL((KER<T, D, 128>), g2, blk, 0, s, q); break; \
-                default: return hipErrorInvalidValue;                                   \
-            }
-            // (the two-query-block kernels are instantiated for d, dv <= 64 only: they spill above)
-#define FA_LAUNCH_C2(KER)                                                               \
-            if constexpr (D <= 64) {                                                    \
-                if (DVc == 32) hipLaunchKernelGGL((KER<T, D, 32>), g2, blk, 0, s, q);   \
-                else hipLaunchKernelGGL((KER<T, D, 64>), g2, blk, 0, s, q);             \
-            }
-            if (q2 && p.wide) { FA_LAUNCH_C2(causal_fwd_w8q2_wide) }
-            else if (q2) { FA_LAUNCH_C2(causal_fwd_w8q2) }
-            else if (p.wide) { FA_LAUNCH_C(causal_fwd_w8b64_wide) }
-            else { FA_LAUNCH_C(causal_fwd_w8b64) }
-#undef FA_LAUNCH_C2
-#undef FA_LAUNCH_C
-            return hipGetLastError();
-        }
-        switch (DVc) {
-            case 32: hipLaunchKernelGGL((dense_fwd_generic<T, D, 32, true>), grid, dim3(kThreads), 0, s, p); break;
-            case 64: hipLaunchKernelGGL((dense_fwd_generic<T, D, 64, true>), grid, dim3(kThreads), 0, s, p); break;
-            case 128: hipLaunchKernelGGL((dense_fwd_generic<T, D, 128, true>), grid, dim3(kThreads), 0, s, p); break;
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    if (p.fast && (g_fwd_variant == 30 || (g_fwd_variant == 0 && D == 128 && DVc == 128))) {
-        hipError_t e = hipSuccess;
-        if (launch_dense_fwd_p4(p, D, DVc, std::is_same<T, bf16>::value ? FA_DTYPE_BF16 : FA_DTYPE_F16, s, &e)) {
-            g_fwd_last_path = 30;
-            return e;
-        }
-    }
-    if (p.fast) {
-        // geometry per head-dim class (measured on MI355X):
-        // <= 64: 8 waves x 2 query blocks (512 rows / workgroup); 128: 8 waves x 1.
-        int v = g_fwd_variant;
-        // default geometries stage Q / O through LDS when the shape allows (variant 20:
-        // the same geometries with per-element Q gathers / O stores, for A/B)
-        const bool wide = p.wide && (v == 0 || v == 5 || v == 7 || v == 30);
-        if (v == 0 || v == 20 || v == 30) v = (D <= 64 && DVc <= 64) ? 7 : 5;
-        const int nw = 8;
-        const int rows = v == 7 ? 512 : 256;   // query rows per workgroup: w8q2 / w8b64
-        FwdParams q = p;
-        q.nqb = (q.N + rows - 1) / rows;
-        q.total_wg = q.nqb * (int)(p.total_wg / p.nqb) * (q.nsplit > 1 ? q.nsplit : 1);
-        const dim3 g2((unsigned)q.total_wg);
-        const dim3 blk(64 * nw);
-#define FA_LAUNCH_T(KER)                                                                \
-        switch (DVc) {                                                                  \
-            case 32: hipLaunchKernelGGL((KER<T, D, 32>), g2, blk, 0, s, q); break;      \
-            case 64: hipLaunchKernelGGL((KER<T, D, 64>), g2, blk, 0, s, q); break;      \
-            case 128: hipLaunchKernelGGL((KER<T, D, 128>), g2, blk, 0, s, q); break;    \
-            default: return hipErrorInvalidValue;                                       \
-        }
-        if (q.nsplit > 1 && rows == 256) { FA_LAUNCH_T(dense_fwd_w8b64_split) }
-        else if (q.nsplit > 1) { FA_LAUNCH_T(dense_fwd_w8q2_split) }
-        else if (v == 5 && wide) { FA_LAUNCH_T(dense_fwd_w8b64_wide) }
-        else if (v == 5) { FA_LAUNCH_T(dense_fwd_w8b64) }
-        else if (wide) { FA_LAUNCH_T(dense_fwd_w8q2_wide) }
-        else { FA_LAUNCH_T(dense_fwd_w8q2) }
-#undef FA_LAUNCH_T
-        if (q.nsplit > 1) {
-            const int64_t total = (int64_t)q.N * q.dv * q.batch;
-            hipLaunchKernelGGL(fwd_split_combine<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, q, total);
-        }
-        return hipGetLastError();
-    }
-    switch (DVc) {
-        case 32: hipLaunchKernelGGL((dense_fwd_generic<T, D, 32>), grid, dim3(kThreads), 0, s, p); break;
-        case 64: hipLaunchKernelGGL((dense_fwd_generic<T, D, 64>), grid, dim3(kThreads), 0, s, p); break;
-        case 128: hipLaunchKernelGGL((dense_fwd_generic<T, D, 128>), grid, dim3(kThreads), 0, s, p); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-template <int D>
-static hipError_t launch_dv_f32(const FwdParams& p, int DVc, dim3 grid, hipStream_t s) {
-    if (p.causal) {
-        switch (DVc) {
-            case 32: hipLaunchKernelGGL((dense_fwd_generic_f32<D, 32, true>), grid, dim3(kThreads), 0, s, p); break;
-            case 64: hipLaunchKernelGGL((dense_fwd_generic_f32<D, 64, true>), grid, dim3(kThreads), 0, s, p); break;
-            case 128: hipLaunchKernelGGL((dense_fwd_generic_f32<D, 128, true>), grid, dim3(kThreads), 0, s, p); break;
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    switch (DVc) {
-        case 32: hipLaunchKernelGGL((dense_fwd_generic_f32<D, 32>), grid, dim3(kThreads), 0, s, p); break;
-        case 64: hipLaunchKernelGGL((dense_fwd_generic_f32<D, 64>), grid, dim3(kThreads), 0, s, p); break;
-        case 128: hipLaunchKernelGGL((dense_fwd_generic_f32<D, 128>), grid, dim3(kThreads), 0, s, p); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-template <class T>
-static hipError_t launch_typed(const FwdParams& p, int Dc, int DVc, dim3 grid, hipStream_t s) {
-    switch (Dc) {
-        case 32: return launch_dv<T, 32>(p, DVc, grid, s);
-        case 64: return launch_dv<T, 64>(p, DVc, grid, s);
-        case 128: return launch_dv<T, 128>(p, DVc, grid, s);
-    }
-    return hipErrorInvalidValue;
-}
-static hipError_t launch_f32(const FwdParams& p, int Dc, int DVc, dim3 grid, hipStream_t s) {
-    switch (Dc) {
-        case 32: return launch_dv_f32<32>(p, DVc, grid, s);
-        case 64: return launch_dv_f32<64>(p, DVc, grid, s);
-        case 128: return launch_dv_f32<128>(p, DVc, grid, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-static bool aligned16(const void* ptr) { return ((uintptr_t)ptr & 15u) == 0; }
-
-// Padded-key fast path: bf16/fp16 K and V are copied into zero-padded slabs of
-// row stride Nk8 = roundup(Nk, 8) in the caller's workspace; the fast kernels
-// then address rows by ldk = Nk8 and mask keys >= Nk as for any ragged last
-// tile.  fa_dense_fwd_workspace reserves that copy only when the SHAPE needs it
-// (Nk % 8 != 0): the query has no pointers.  K / V that are not 16-B aligned
-// with Nk % 8 == 0 (e.g. a view at an odd element offset) take the same copy
-// when the workspace passed is large enough for it (fwd_pad_bytes_any), and the
-// generic kernel otherwise.  Without a workspace (fa_dense_fwd) those shapes run
-// the generic kernel.
-static bool fwd_pad_fits(int dtype, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    const int64_t nk8 = (Nk + 7) / 8 * 8;
-    return dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_F64 && nk8 * d * 2 < INT32_MAX && nk8 * dv * 2 < INT32_MAX &&
-           nk8 * (d > dv ? d : dv) * batch < ((int64_t)1 << 40);
-}
-static bool fwd_pad_needed(int dtype, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    return Nk % 8 != 0 && fwd_pad_fits(dtype, Nk, d, dv, batch);
-}
-static size_t fwd_pad_bytes_any(int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    const int64_t nk8 = (Nk + 7) / 8 * 8;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    return al((size_t)(nk8 * d * batch) * 2) + al((size_t)(nk8 * dv * batch) * 2) + 256;
-}
-static size_t fwd_pad_bytes(int dtype, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    if (!fwd_pad_needed(dtype, Nk, d, dv, batch)) return 0;
-    return fwd_pad_bytes_any(Nk, d, dv, batch);
-}
-size_t dense_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    return fwd_pad_bytes(dtype, Nk, d, dv, batch) + split_plan(dtype, N, Nk, d, dv, batch).bytes;
-}
-// fa_causal_fwd: the padded K / V copies only (causal launches never split the keys)
-size_t causal_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    return fwd_pad_bytes(dtype, Nk, d, dv, batch);
-}
 // dst (Np, C, B) <- src (N, C, B), zero rows n >= N
 template <class T>
 __global__ __launch_bounds__(256) void fwd_pad_keys(const T* __restrict__ src, T* __restrict__ dst, int N, int Np,
@@ -1224,9 +1027,84 @@ __global__ __launch_bounds__(256) void fwd_pad_keys(const T* __restrict__ src, T
     dst[e] = n < N ? src[cb * N + n] : (T)0.0f;
 }
 
+// --------------------------------------------------------------------------
+// launcher: dense_fwd_plan (fa_dense_plan.h) names the kernel, its grid and the
+// workspace offsets; nothing below decides any of them again
+// --------------------------------------------------------------------------
+static_assert(kBM == kFwdGenericRows && kThreads == kFwdGenericThreads && kBN == kFwdKeyTile, "the plan's constants");
+
+hipError_t launch_dense_fwd_p4(const FwdParams& p, int Dc, int dtype, dim3 grid, hipStream_t s);
+
+// The bf16 / fp16 kernel of a plan at head-dim classes (Dc, DVc).  Every kernel is
+// instantiated for the nine class pairs, the d = 128 forms of w8q2 included (a forced
+// kFwdW8Q2 reaches them), except the causal two-query-block kernels: d, dv <= 64 only (they
+// spill above, and the plan picks them only there).
+template <class T>
+static hipError_t launch_16bit(const DenseFwdPlan& pl, const FwdParams& p, int Dc, int DVc, hipStream_t s) {
+    const dim3 grid((unsigned)pl.grid), blk(pl.block);
+    const bool causal = pl.causal != 0;
+    auto go = [&](void (*kernel)(FwdParams)) { hipLaunchKernelGGL(kernel, grid, blk, 0, s, p); };
+    hipError_t e = hipErrorInvalidValue;   // stays when a class or the kernel is not one of ours
+    by_dim_class(Dc, [&](auto Dk) {
+        by_dim_class(DVc, [&](auto DVk) {
+            constexpr int D = decltype(Dk)::value, DV = decltype(DVk)::value;
+            switch (pl.kernel) {
+                case kDenseFwdGeneric: go(causal ? dense_fwd_generic<T, D, DV, true> : dense_fwd_generic<T, D, DV>); break;
+                case kDenseFwdW8B64: go(causal ? causal_fwd_w8b64<T, D, DV> : dense_fwd_w8b64<T, D, DV>); break;
+                case kDenseFwdW8B64Wide: go(causal ? causal_fwd_w8b64_wide<T, D, DV> : dense_fwd_w8b64_wide<T, D, DV>); break;
+                case kDenseFwdW8Q2:
+                    if constexpr (D <= 64 && DV <= 64) go(causal ? causal_fwd_w8q2<T, D, DV> : dense_fwd_w8q2<T, D, DV>);
+                    else go(dense_fwd_w8q2<T, D, DV>);
+                    break;
+                case kDenseFwdW8Q2Wide:
+                    if constexpr (D <= 64 && DV <= 64) go(causal ? causal_fwd_w8q2_wide<T, D, DV> : dense_fwd_w8q2_wide<T, D, DV>);
+                    else go(dense_fwd_w8q2_wide<T, D, DV>);
+                    break;
+                case kDenseFwdW8B64Split: go(dense_fwd_w8b64_split<T, D, DV>); break;
+                case kDenseFwdW8Q2Split: go(dense_fwd_w8q2_split<T, D, DV>); break;
+                default: return;
+            }
+            if (pl.nsplit > 1) {
+                const int64_t total = (int64_t)p.N * p.dv * p.batch;
+                hipLaunchKernelGGL(fwd_split_combine<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p, total);
+            }
+            e = hipGetLastError();
+        });
+    });
+    return e;
+}
+static hipError_t launch_f32(const DenseFwdPlan& pl, const FwdParams& p, int Dc, int DVc, hipStream_t s) {
+    hipError_t e = hipErrorInvalidValue;
+    by_dim_class(Dc, [&](auto Dk) {
+        by_dim_class(DVc, [&](auto DVk) {
+            constexpr int D = decltype(Dk)::value, DV = decltype(DVk)::value;
+            void (*kernel)(FwdParams) = pl.causal ? dense_fwd_generic_f32<D, DV, true> : dense_fwd_generic_f32<D, DV>;
+            hipLaunchKernelGGL(kernel, dim3((unsigned)pl.grid), dim3(pl.block), 0, s, p);
+            e = hipGetLastError();
+        });
+    });
+    return e;
+}
+template <class T>
+static void pad_keys(const void* src, void* dst, int64_t Nk, int64_t ldk, int64_t C, int64_t B, hipStream_t s) {
+    const int64_t total = ldk * C * B;
+    hipLaunchKernelGGL(fwd_pad_keys<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const T*)src, (T*)dst,
+                       (int)Nk, (int)ldk, total);
+}
+
+// The shape's own needs (aligned tensors, the auto variant, room for everything): the
+// queries have no pointers, and the CU count does not change the total.
+size_t dense_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
+    return dense_fwd_plan(dtype, N, Nk, d, dv, batch, false, {kFwdAuto, 0}, true, true, SIZE_MAX, 0).total;
+}
+// fa_causal_fwd: the padded K / V copies only (causal launches never split the keys)
+size_t causal_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
+    return dense_fwd_plan(dtype, N, Nk, d, dv, batch, true, {kFwdAuto, 0}, true, true, SIZE_MAX, 0).total;
+}
+
 int launch_dense_fwd(const DenseArgs& a, hipStream_t s, const char** why) {
     g_fwd_last_path = 0;   // every path below that is not a persistent kernel leaves 0
-    if (a.dtype == FA_DTYPE_F64) return launch_dense_fwd_f64(a, s, why);
+    if (a.dtype == FA_DTYPE_F64) return launch_dense_fwd_f64(a, s, why);   // kDenseFwdF64: it makes its own checks
     const int Dc = head_dim_class(a.d), DVc = head_dim_class(a.dv);
     if (!Dc || !DVc) {
         *why = "head dimension exceeds the compiled maximum (128)";
@@ -1241,80 +1119,60 @@ int launch_dense_fwd(const DenseArgs& a, hipStream_t s, const char** why) {
         *why = "per-slab extent exceeds 2^31 elements";
         return FA_ERR_UNSUPPORTED;
     }
-    FwdParams p;
-    p.Q = a.Q; p.K = a.K; p.V = a.V; p.O = a.O; p.l = a.l; p.m = a.m;
-    p.N = (int)a.N; p.Nk = (int)a.Nk; p.d = (int)a.d; p.dv = (int)a.dv;
-    p.nqb = (int)((a.N + kBM - 1) / kBM);
-    const int64_t total = (int64_t)p.nqb * a.batch;
-    if (total > INT32_MAX) {
+    if ((a.N + kBM - 1) / kBM * a.batch > INT32_MAX) {
         *why = "grid too large";
         return FA_ERR_UNSUPPORTED;
     }
-    p.total_wg = (int)total;
+    if (a.dtype != FA_DTYPE_F32 && !dense_16bit(a.dtype)) {
+        *why = "unknown dtype";
+        return FA_ERR_INVALID_ARG;
+    }
+    const DenseFwdPlan pl = dense_fwd_plan(a.dtype, a.N, a.Nk, a.d, a.dv, a.batch, a.causal != 0,
+                                           {g_fwd_variant, g_causal_rev}, aligned16(a.K) && aligned16(a.V),
+                                           aligned16(a.Q) && aligned16(a.O), a.workspace ? a.workspace_bytes : 0,
+                                           device_cus(s));
+    char* const w = al256(a.workspace);
+    FwdParams p;
+    p.Q = a.Q; p.K = a.K; p.V = a.V; p.O = a.O; p.l = a.l; p.m = a.m;
+    p.N = (int)a.N; p.Nk = (int)a.Nk; p.d = (int)a.d; p.dv = (int)a.dv;
+    p.ldk = (int)pl.ldk;
+    p.nqb = (int)pl.nqb;
+    p.total_wg = (int)pl.total_wg;
     p.scale = a.scale;
     p.scale_log2 = a.scale * kLog2e;
     p.rescale_log2 = g_fwd_rescale_log2;
     p.batch = (int)a.batch;
-    p.nsplit = 1; p.tps = 0; p.opart = p.lpart = p.mpart = nullptr;
-    p.causal = a.causal ? (g_causal_rev ? 3 : 1) : 0;   // (launch_dv turns order 2 into bit 2 where it applies)
-    const int epc = a.dtype == FA_DTYPE_F32 ? 4 : 8;
-    p.ldk = (int)a.Nk;
-    p.fast = (a.Nk % epc == 0) && aligned16(a.K) && aligned16(a.V);
-    p.wide = a.N % 8 == 0 && aligned16(a.Q) && aligned16(a.O);
-    // bytes of the workspace taken by the padded K / V copies (0: none made)
-    size_t pad_bytes = 0;
-    if (!p.fast && a.workspace && fwd_pad_fits(a.dtype, a.Nk, a.d, a.dv, a.batch) &&
-        a.N * a.d * 2 < (int64_t)INT32_MAX &&
-        a.workspace_bytes >= fwd_pad_bytes_any(a.Nk, a.d, a.dv, a.batch)) {
-        pad_bytes = fwd_pad_bytes_any(a.Nk, a.d, a.dv, a.batch);
-        const int64_t nk8 = (a.Nk + 7) / 8 * 8;
-        char* w = (char*)(((uintptr_t)a.workspace + 255) & ~(uintptr_t)255);
-        char* kp = w;
-        char* vp = w + (((size_t)(nk8 * a.d * a.batch) * 2 + 255) & ~(size_t)255);
-        const int64_t tk = nk8 * a.d * a.batch, tv = nk8 * a.dv * a.batch;
+    p.nsplit = pl.nsplit; p.tps = pl.tps; p.opart = p.lpart = p.mpart = nullptr;
+    p.causal = pl.causal;
+    p.fast = pl.kv_vec;
+    p.wide = pl.wide;
+    if (pl.pad) {
+        void* const kp = w + pl.off_k;
+        void* const vp = w + pl.off_v;
         if (a.dtype == FA_DTYPE_F16) {
-            hipLaunchKernelGGL(fwd_pad_keys<f16>, dim3((unsigned)((tk + 255) / 256)), dim3(256), 0, s, (const f16*)a.K, (f16*)kp, (int)a.Nk, (int)nk8, tk);
-            hipLaunchKernelGGL(fwd_pad_keys<f16>, dim3((unsigned)((tv + 255) / 256)), dim3(256), 0, s, (const f16*)a.V, (f16*)vp, (int)a.Nk, (int)nk8, tv);
+            pad_keys<f16>(a.K, kp, a.Nk, pl.ldk, a.d, a.batch, s);
+            pad_keys<f16>(a.V, vp, a.Nk, pl.ldk, a.dv, a.batch, s);
         } else {
-            hipLaunchKernelGGL(fwd_pad_keys<bf16>, dim3((unsigned)((tk + 255) / 256)), dim3(256), 0, s, (const bf16*)a.K, (bf16*)kp, (int)a.Nk, (int)nk8, tk);
-            hipLaunchKernelGGL(fwd_pad_keys<bf16>, dim3((unsigned)((tv + 255) / 256)), dim3(256), 0, s, (const bf16*)a.V, (bf16*)vp, (int)a.Nk, (int)nk8, tv);
+            pad_keys<bf16>(a.K, kp, a.Nk, pl.ldk, a.d, a.batch, s);
+            pad_keys<bf16>(a.V, vp, a.Nk, pl.ldk, a.dv, a.batch, s);
         }
         p.K = kp;
         p.V = vp;
-        p.ldk = (int)nk8;
-        p.fast = 1;
     }
-    // buffer descriptors address a slab with 32-bit byte offsets
-    const int64_t esz = a.dtype == FA_DTYPE_F32 ? 4 : 2;
-    if (a.N * a.d * esz >= (int64_t)INT32_MAX || (int64_t)p.ldk * a.d * esz >= (int64_t)INT32_MAX ||
-        (int64_t)p.ldk * a.dv * esz >= (int64_t)INT32_MAX)
-        p.fast = 0;
-    // split-KV for small grids (fast kernels, default geometry, workspace given)
-    // (not when fa_fwd_p4's own 256-row blocks already fill the chip)
-    const bool p4_fills = (g_fwd_variant == 30 || (g_fwd_variant == 0 && Dc == 128 && DVc == 128)) &&
-                          (a.N + 255) / 256 * a.batch >= device_cus(s);
-    if (p.fast && !a.causal && (g_fwd_variant == 0 || g_fwd_variant == 30) && !p4_fills && a.workspace) {
-        const SplitPlan sp = split_plan(a.dtype, a.N, a.Nk, a.d, a.dv, a.batch);
-        if (sp.nsplit > 1 && a.workspace_bytes >= pad_bytes + sp.bytes) {
-            auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-            char* w = (char*)(((uintptr_t)a.workspace + 255) & ~(uintptr_t)255) + (pad_bytes ? pad_bytes - 256 : 0);
-            w = (char*)(((uintptr_t)w + 255) & ~(uintptr_t)255);
-            p.opart = (float*)w;
-            w += al((size_t)(sp.nsplit * a.batch * a.N * a.dv) * 4);
-            p.lpart = (float*)w;
-            w += al((size_t)(sp.nsplit * a.batch * a.N) * 4);
-            p.mpart = (float*)w;
-            p.nsplit = sp.nsplit;
-            p.tps = sp.tps;
-        }
+    if (pl.nsplit > 1) {
+        p.opart = (float*)(w + pl.off_opart);
+        p.lpart = (float*)(w + pl.off_lpart);
+        p.mpart = (float*)(w + pl.off_mpart);
     }
-    const dim3 grid((unsigned)total);
     hipError_t e;
-    switch (a.dtype) {
-        case FA_DTYPE_BF16: e = launch_typed<bf16>(p, Dc, DVc, grid, s); break;
-        case FA_DTYPE_F16: e = launch_typed<f16>(p, Dc, DVc, grid, s); break;
-        case FA_DTYPE_F32: e = launch_f32(p, Dc, DVc, grid, s); break;
-        default: *why = "unknown dtype"; return FA_ERR_INVALID_ARG;
+    switch (pl.kernel) {
+        case kDenseFwdGenericF32: e = launch_f32(pl, p, Dc, DVc, s); break;
+        case kDenseFwdP4:
+            e = launch_dense_fwd_p4(p, Dc, a.dtype, dim3((unsigned)pl.grid), s);
+            g_fwd_last_path = 30;
+            break;
+        default:
+            e = a.dtype == FA_DTYPE_F16 ? launch_16bit<f16>(pl, p, Dc, DVc, s) : launch_16bit<bf16>(pl, p, Dc, DVc, s);
     }
     if (e != hipSuccess) {
         *why = hipGetErrorString(e);

@@ -32,11 +32,12 @@
 //
 // Taken for the LDS-staged fast shapes (bf16/f16, Nk % 8 == 0, N % 8 == 0, 16-B
 // aligned tensors), d = dv = 64 or 128, at least one block per CU and enough key
-// tiles per block for the Q prefetch (launch_dense_fwd_p4).
+// tiles per block for the Q prefetch (dense_fwd_plan's kDenseFwdP4, fa_dense_plan.h).
 #include <type_traits>
 
 #include "fa_common.h"
 #include "fa_internal.h"
+#include "fa_dense_plan.h"
 #include "fa_fwd_params.h"
 #include "../../include/fa_hip.h"
 
@@ -723,31 +724,17 @@ __global__ __launch_bounds__(256, 1) void dense_fwd_p4(FwdParams p) {
     }
 }
 
-// Launch on the persistent grid; returns false when the shape is not this kernel's.
-bool launch_dense_fwd_p4(const FwdParams& p, int Dc, int DVc, int dtype, hipStream_t s, hipError_t* err) {
-    if (!p.fast || !p.wide || p.nsplit > 1 || Dc != DVc || p.d != Dc || p.dv != DVc) return false;
-    const int cus = device_cus(s);
-    if (cus <= 0) return false;
-    // the Q prefetch goes out in phases B(0 .. QP-1) of the previous block; whole key tiles
-    if (p.Nk % 64 != 0 || p.Nk / 64 < Dc / 8 + 1 || p.ldk != p.Nk) return false;
-    FwdParams q = p;
-    q.nqb = (p.N + kP4Rows - 1) / kP4Rows;
-    const int64_t nblk = (int64_t)q.nqb * p.batch;
-    if (nblk < cus || nblk > INT32_MAX / 2) return false;
-    q.total_wg = (int)nblk;
-    const dim3 grid((unsigned)cus), blk(256);
-#define FA_P4_LAUNCH(TT)                                                                                         \
-    switch (Dc) {                                                                                                \
-        case 64: hipLaunchKernelGGL((dense_fwd_p4<TT, 64, 64>), grid, blk, 0, s, q); break;                     \
-        case 128: hipLaunchKernelGGL((dense_fwd_p4<TT, 128, 128>), grid, blk, 0, s, q); break;                  \
-        default: return false;                                                                                   \
-    }
-    if (dtype == FA_DTYPE_BF16) { FA_P4_LAUNCH(bf16) }
-    else if (dtype == FA_DTYPE_F16) { FA_P4_LAUNCH(f16) }
-    else return false;
-#undef FA_P4_LAUNCH
-    *err = hipGetLastError();
-    return true;
+// Launch on the persistent grid (one workgroup per CU).  Which shapes come here is
+// dense_fwd_plan's kDenseFwdP4 (fa_dense_plan.h); p carries its nqb and total_wg.
+static_assert(kP4Rows == kFwdP4Rows, "the plan's constants");
+hipError_t launch_dense_fwd_p4(const FwdParams& p, int Dc, int dtype, dim3 grid, hipStream_t s) {
+    const bool half = dtype == FA_DTYPE_F16;
+    void (*kernel)(FwdParams);
+    if (Dc == 64) kernel = half ? dense_fwd_p4<f16, 64, 64> : dense_fwd_p4<bf16, 64, 64>;
+    else if (Dc == 128) kernel = half ? dense_fwd_p4<f16, 128, 128> : dense_fwd_p4<bf16, 128, 128>;
+    else return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kernel, grid, dim3(kFwdP4Threads), 0, s, p);
+    return hipGetLastError();
 }
 
 }  // namespace fa

@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace fa {
 
 struct DenseArgs {
@@ -158,16 +160,38 @@ inline int head_dim_class(int64_t d) {
 
 constexpr int kMaxHeadDim = 128;
 
+// Workspace regions start on 256-B boundaries; the vector paths want 16-B aligned tensors.
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+inline char* al256(void* p) { return (char*)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+// A run-time head-dim class as a compile-time constant for the launchers: by_dim_class calls
+// f(dim_c<C>{}) with the class c (32, 64 or 128; false, and no call, for anything else).  f
+// is a generic lambda, [&](auto D), that names kernel<..., D> or decltype(D)::value.  (A
+// CAUSAL twin needs no such dispatcher: kernels of one signature are picked as function
+// pointers, causal ? kernel<..., true> : kernel<...>.)
+template <int N>
+using dim_c = std::integral_constant<int, N>;
+template <class F>
+inline bool by_dim_class(int c, F&& f) {
+    switch (c) {
+        case 32: f(dim_c<32>{}); return true;
+        case 64: f(dim_c<64>{}); return true;
+        case 128: f(dim_c<128>{}); return true;
+    }
+    return false;
+}
+
 // Debug / benchmark knobs (fa_debug_set_*; not part of include/fa_hip.h and not
 // ABI state).  They are THREAD-LOCAL: a knob set on one host thread changes only
 // the kernels that thread launches, so concurrent callers on other threads stay
 // on the default paths and the public entry points remain stateless for them.
-extern thread_local int g_fwd_variant;        // forward kernel variant
+extern thread_local int g_fwd_variant;        // forward kernel variant (a DenseFwdVariant, fa_dense_plan.h)
 extern thread_local int g_fwd_last_path;      // 30 when the last fast forward launch ran fa_fwd_p4
 extern thread_local float g_fwd_rescale_log2; // forward fast kernels: lazy-rescale threshold (log2 units)
 extern thread_local int g_causal_rev;         // causal fast forward: launch order of the query blocks (0, 1, 2: fa_debug_set_causal_order)
 extern thread_local int g_bwd_force_generic;  // backward: force the generic SIMT path
-extern thread_local int g_bwd_mode;           // backward MFMA path: 0 auto, 1 split passes, 2 single pass
+extern thread_local int g_bwd_mode;           // backward MFMA path (a DenseBwdMode, fa_dense_plan.h: kBwdAuto, kBwdTwoPass, kBwdSinglePass, ...)
 extern thread_local int g_bwd_l2local;        // single pass: running sums handed over in the XCD's L2
 extern thread_local int g_bwd_hoff;           // single pass: step offset between consecutive members
 extern thread_local int g_bwd_stall_us;       // single pass: no-progress bound of a poll (us)

@@ -387,13 +387,10 @@ static int hip_status(hipError_t e, const char** why) {
 }
 static int launch_status(const char** why) { return hip_status(hipGetLastError(), why); }
 
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 // Calls f(D, DV) with the head-dim classes the d, dv <= 64 kernels are compiled for
 // (32 or 64 each) as integral constants: f is a generic lambda, [&](auto D, auto DV),
-// that names kernel<..., D, DV> (the constants convert to int at compile time).
-template <int N>
-using dim_c = std::integral_constant<int, N>;
+// that names kernel<..., D, DV> (the constants, dim_c of fa_internal.h, convert to int at
+// compile time).
 template <class F>
 static void by_head_class(int64_t d, int64_t dv, F&& f) {
     if (d <= 32) {

@@ -278,8 +278,8 @@ def dense_fa_(O: torch.Tensor, l: torch.Tensor, m: torch.Tensor,
     if (code in (DTYPES[torch.bfloat16], DTYPES[torch.float16]) and N * Nk * B > 0 and Nk % 8 == 0
             and (K.data_ptr() % 16 or V.data_ptr() % 16)):
         # K / V not 16-B aligned (a view at an odd offset): add room for the
-        # padded K / V copies the fast kernels then run on (fa_fwd.hip
-        # fwd_pad_bytes_any); the shape-only workspace query cannot see pointers
+        # padded K / V copies the fast kernels then run on (fa_dense_plan.h
+        # dense_fwd_plan); the shape-only workspace query cannot see pointers
         al = lambda x: (x + 255) & ~255
         nws += al(Nk * d * B * 2) + al(Nk * dv * B * 2) + 256
     if nws == 0:

@@ -51,10 +51,13 @@ extern "C" int p4_launch(int dtype, const void* Q, const void* K, const void* V,
     p.scale_log2 = p.scale * fa::kLog2e;
     p.rescale_log2 = fa::kRescaleLog2;
     p.fast = 1; p.wide = 1; p.nsplit = 1;
-    p.nqb = (N + 255) / 256;
-    p.total_wg = p.nqb * batch;
-    hipError_t e = hipSuccess;
-    if (!fa::launch_dense_fwd_p4(p, d, d, dtype, (hipStream_t)stream, &e)) return 5;
+    // the shapes p4 takes are the plan's: forced variant kFwdP4, aligned tensors
+    const fa::DenseFwdPlan pl = fa::dense_fwd_plan(dtype, N, N, d, d, batch, false, {fa::kFwdP4, 0}, true, true, 0,
+                                                   fa::device_cus((hipStream_t)stream));
+    if (pl.kernel != fa::kDenseFwdP4) return 5;
+    p.nqb = (int)pl.nqb;
+    p.total_wg = (int)pl.total_wg;
+    const hipError_t e = fa::launch_dense_fwd_p4(p, d, dtype, dim3((unsigned)pl.grid), (hipStream_t)stream);
     return e == hipSuccess ? 0 : 6;
 }
 #ifdef P4_SLOTS
