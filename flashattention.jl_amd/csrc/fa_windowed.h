@@ -519,10 +519,14 @@ inline WinFwdKernel win_fwd_plan(int dtype, const WindowGeom& g, int64_t d, int6
         const int64_t nstrip = win_strips(g, batch);
         if (nstrip < INT32_MAX && (mode == kWinStrip || nstrip >= kStripMin)) return kWinFwdStrip;
     }
-    const bool two_img_ok = 2 * g.P * dmax * 2 < INT32_MAX;
-    // the auto rule looks at the window count only, not at the geometry: ADVICE.md
+    // win_rows1s addresses its NWIN windows by 32-bit byte offsets from the workgroup's first
+    // image, over up to NWIN images (one window per image): those images' bytes stay below 2^31
+    const bool two_img_ok = 2 * g.P * dmax * 2 < INT32_MAX, three_img_ok = 3 * g.P * dmax * 2 < INT32_MAX;
+    // The auto rule looks at the window count only (kRows3Min's measurements), not at the
+    // geometry: any windows-per-image count is right, since the kernel's descriptors span the
+    // three images a triple can touch; images too large for that take two per workgroup.
     const bool three = mode == kWinThree || (mode == kWinAuto && nw >= kRows3Min && nw < kRows3Max);
-    if (three && two_img_ok) return kWinFwdShift3;
+    if (three && three_img_ok) return kWinFwdShift3;
     if (mode != kWinOne && two_img_ok) return kWinFwdShift2;
     return kWinFwdShift1;
 }

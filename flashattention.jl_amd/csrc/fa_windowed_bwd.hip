@@ -76,9 +76,10 @@ __global__ __launch_bounds__(256 * NWIN) void win_bwd_rows(const T* __restrict__
     // staging item it -> (window it % NWIN, feature (it / NWIN) >> 3, slot row (it / NWIN) & 7): the
     // NWIN windows' loads of one (feature, row) sit on adjacent lanes, 2·ws bytes apart, and share
     // their cache lines; every item of a lane belongs to window tid % NWIN (NTH % NWIN == 0).
-    // Descriptors span the first window's image and the next (a pair may straddle images).
+    // Descriptors span the images the workgroup's windows can span (NWIN, clamped to the
+    // batch: a pair may straddle images), as in win_rows1s.
     const int b0 = win_of(0).b;
-    const int nimg = min(NWIN == 1 ? 1 : 2, nwin_total / nperimg - b0);
+    const int nimg = min(NWIN, nwin_total / nperimg - b0);
     const int wl_me = NWIN == 1 ? 0 : (int)(tid % NWIN);
     const Win wme = win_of(wl_me);
     auto item_off = [&](int it, int C) {

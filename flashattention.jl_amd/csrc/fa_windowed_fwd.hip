@@ -594,10 +594,11 @@ __global__ __launch_bounds__(256 * NWIN) void win_rows1s(const T* __restrict__ q
     };
 
     // item it -> (window it % NWIN, feature f = (it / NWIN) >> 3, slot row yy = (it / NWIN) & 7)
-    // descriptors over the workgroup's first image and the next one (a window
-    // pair may straddle images); item offsets are relative to image b0
+    // descriptors over the images the workgroup's windows can span: NWIN of them when
+    // every image holds one window, clamped to the batch; item offsets are relative to
+    // image b0 (32-bit: win_fwd_plan keeps NWIN images' bytes below 2^31)
     const int b0 = win_of(0).b;
-    const int nimg = min(NWIN == 1 ? 1 : 2, (int)nwin_total / nperimg - b0);
+    const int nimg = min(NWIN, (int)nwin_total / nperimg - b0);
     // every item of a lane belongs to the same window (NTH is a multiple of NWIN)
     const int wl_me = NWIN == 1 ? 0 : (int)(tid % NWIN);
     const Win wme = win_of(wl_me);

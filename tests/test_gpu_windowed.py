@@ -88,6 +88,29 @@ def test_config3_full_size(fa):
     assert_lm_close(_np(m), mr, "bfloat16", "m")
 
 
+def test_config2_forward_B1_full_image(fa):
+    """BASELINE configs[2] at B = 1, the call bench.py times: auto mode takes the row-shift
+    kernel with two windows per workgroup (361 windows, 57 strips: below the three-window
+    and strip rules); y, l and m against the oracle on the full image."""
+    import ctypes
+    L = fa.lib()
+    i64, ci = ctypes.c_int64, ctypes.c_int
+    L.fa_debug_win_fwd_plan.restype = ci
+    L.fa_debug_win_fwd_plan.argtypes = [ci, ci, ctypes.POINTER(i64), i64, i64, i64, i64, i64, i64, ci, ci, ci]
+    kern = L.fa_debug_win_fwd_plan(fa.DTYPES[torch.bfloat16], 2, (i64 * 2)(128, 128), 64, 64, 1, 7, 7, 3, 0, 1, 1)
+    assert kern == 6, f"planned fa::WinFwdKernel {kern}, not kWinFwdShift2"
+    rng = np.random.default_rng(23)
+    bf = lambda a: torch.tensor(a).to(torch.bfloat16).double().numpy()
+    q, k, v = (bf(rng.standard_normal((128, 128, 64, 1))) for _ in range(3))
+    y, l, m = fa.windowed_fa(*(fa.jl_tensor(a, torch.bfloat16) for a in (q, k, v)), 7)
+    torch.cuda.synchronize()
+    yr, lr, mr = O.windowed_fa(q, k, v, 7, 7, 3)
+    assert l.shape == (49, 1, 361, 1)
+    assert_close(_np(y), yr, "bfloat16", "y", nan_ok=True)
+    assert_lm_close(_np(l), lr, "bfloat16", "l")
+    assert_lm_close(_np(m), mr, "bfloat16", "m")
+
+
 @pytest.mark.parametrize("B,mode", [(1, 0), (1, 3), (3, 13)])
 def test_config2_backward_full_size_window_pairing(fa, B, mode):
     """BASELINE configs[2] backward on the full image against the oracle's chain rule,

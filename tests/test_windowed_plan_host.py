@@ -2,7 +2,8 @@
 which kernel a shape gets.  The GPU parity tests pass whichever kernel runs; this table pins
 the choice.  It was written by hand from the dispatch rules (the thresholds kRows4Min 1024,
 kStripMin / kStripBwdMin 256, kRows3Min 600 / kRows3Max 1000, kBwdPairMaxPerCu 1.5, 256 CUs
-when the device cannot be asked), never by calling the plan.  No device is touched."""
+when the device cannot be asked, two / three images' bytes below 2^31 for two / three windows
+per row-shift workgroup), never by calling the plan.  No device is touched."""
 from __future__ import annotations
 
 import ctypes
@@ -33,6 +34,13 @@ D1_64 = ((256,), 64, 64, 0)      # 1-D, 64 tokens
 D1_128 = ((256,), 128, 128, 0)   # 1-D, 128 tokens
 D3 = ((8, 8, 8), 4, 4, 0)        # 3-D, 64 tokens
 NARROW = ((4, 16), 8, 8, 3)      # S[0] < 8
+# the 8- and 16-pixel-wide strip shapes of tests/test_gpu_windowed_batch_edges.py: one strip per image
+ONE7S = ((8, 7), 7, 7, 0)        # one window per image, first strip k0 = 8; the covered right end x = 7 is in a chunk
+EDGE7 = ((8, 7), 7, 7, 3)        # two windows per image, k0 = 5 aligns the strip ends; right end past the image
+TRI7S = ((16, 7), 7, 7, 3)       # three windows per image, aligned
+# three images of P pixels at 64 features: 3 * P * 64 * 2 bytes on either side of 2^31 (win_rows1s x3's offsets)
+BIG3_IN = ((2360, 2360), 7, 7, 3)    # 2 138 726 400 B
+BIG3_OUT = ((2400, 2400), 7, 7, 3)   # 2 211 840 000 B; two images (1 474 560 000 B) still fit
 
 
 def fwd(geom, B, want, dtype=BF16, d=64, dv=64, mode=0, qkv=1, y=1):
@@ -52,6 +60,12 @@ FWD = [
     # kStripMin, both sides
     fwd(G7_32, 17, F_SHIFT2),                   # 3 * 5 * 17 = 255 strips
     fwd(G7_56, 8, F_STRIP),                     # 2 * 16 * 8 = 256 strips
+    fwd(ONE7S, 255, F_SHIFT2),                  # one strip per image: 255 strips, 255 windows
+    fwd(ONE7S, 256, F_STRIP),
+    fwd(EDGE7, 255, F_SHIFT2),                  # 255 strips, 510 windows
+    fwd(EDGE7, 256, F_STRIP),
+    fwd(TRI7S, 255, F_SHIFT3),                  # 255 strips; 765 windows: three per workgroup
+    fwd(TRI7S, 256, F_STRIP),
     # kRows3Min / kRows3Max, both sides (one window per image, stride != ws)
     fwd(ONE7, 599, F_SHIFT2),
     fwd(ONE7, 600, F_SHIFT3),
@@ -117,10 +131,16 @@ FWD = [
     fwd(G7, 1, F_STRIP, mode=10),
     fwd(G7, 1, F_SHIFT2, mode=10, y=0),
     fwd(S8, 2, F_SHIFT2, mode=10),              # stride != ws
-    # mode 12: three windows per workgroup
+    fwd(ONE7S, 1, F_STRIP, mode=10),            # a single strip of one window
+    fwd(EDGE7, 7, F_STRIP, mode=10),
+    fwd(TRI7S, 2, F_STRIP, mode=10),
+    # mode 12: three windows per workgroup, while three images' bytes fit 32-bit offsets
     fwd(G7, 1, F_SHIFT3, mode=12),
     fwd(G7, 5, F_SHIFT3, mode=12),
     fwd(WS8, 2, F_ROWS1, mode=12),
+    fwd(ONE7, 7, F_SHIFT3, mode=12),            # one window per image: a workgroup spans three images
+    fwd(BIG3_IN, 1, F_SHIFT3, mode=12),
+    fwd(BIG3_OUT, 1, F_SHIFT2, mode=12),
     # mode 13 is the backward's; the forward takes two windows per workgroup
     fwd(G7, 2, F_SHIFT2, mode=13),
     fwd(G7, 5, F_SHIFT2, mode=13),
@@ -144,6 +164,12 @@ BWD = [
     # kStripBwdMin, both sides
     bwd(G7_32, 17, B_ROWS1),                    # 255 strips
     bwd(G7_56, 8, B_STRIP_PARTIAL),             # 256 strips; the covered right end x = 53 is in a chunk
+    bwd(ONE7S, 255, B_ROWS2),                   # 255 strips; 255 windows <= 384
+    bwd(ONE7S, 256, B_STRIP_PARTIAL),           # the covered right end x = 7 is in a chunk
+    bwd(ONE7S, 257, B_STRIP_PARTIAL),
+    bwd(EDGE7, 255, B_ROWS1),                   # 255 strips; 510 windows > 384
+    bwd(EDGE7, 256, B_STRIP),                   # k0 = 5 aligns the ends, the right end is past the image
+    bwd(TRI7S, 256, B_STRIP),
     # kBwdPairMaxPerCu, both sides; 256 CUs when the device cannot be asked
     bwd(ONE7, 384, B_ROWS2),
     bwd(ONE7, 385, B_ROWS1),
@@ -177,6 +203,9 @@ BWD = [
     bwd(G7, 1, B_STRIP, mode=10),
     bwd(S8, 2, B_ROWS1, mode=10),               # stride != ws; a forced mode never pairs
     bwd(G7, 1, B_ROWS1, mode=10, grads=0),
+    bwd(ONE7S, 1, B_STRIP_PARTIAL, mode=10),
+    bwd(EDGE7, 7, B_STRIP, mode=10),
+    bwd(TRI7S, 2, B_STRIP, mode=10),
     # mode 13: two windows per workgroup at any size
     bwd(G7, 2, B_ROWS2, mode=13),
     bwd(G7, 5, B_ROWS2, mode=13),
