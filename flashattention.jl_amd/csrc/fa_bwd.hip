@@ -43,6 +43,10 @@ struct BwdParams {
     float* nD;     // workspace: −rowsum(dO ∘ O)          [batch][N]
     float* nlse;   // workspace: −(m + ln l)/τ (raw units) [batch][N]
     int N, Nk, d, dv, batch;
+    // the caller's key count.  The padded path runs on Nk rounded up to 8: the zero rows
+    // j >= nkv are masked (P = 0) where a dQ is summed, not left to P * 0: with every real
+    // score far below 0 their P = exp(0 - lse) overflows (fp16 dS from lse < -11 on)
+    int nkv = 0;
     int nblk, total_wg;          // fast path: row blocks per slab, workgroups
     float scale, scale_log2;
     double scale64 = 0.0;        // Float64 generic path: τ in double
@@ -306,8 +310,9 @@ __global__ __launch_bounds__(kGThreads) void bwd_generic_dkdv(BwdParams p) {
 // is exactly what a 32x32x2 B operand with k = h needs (cf. the fp32 forward).
 //   dK/dV: S = Q Kᵀ (queries on rows, keys on lanes), dVᵀ += dOᵀ P, dKᵀ += Qᵀ dS;
 //   dQ   : Sᵀ = K Qᵀ (keys on rows, queries on lanes), dQᵀ += Kᵀ dSᵀ.
-// Keys past Nk are zero rows: their own rows are not stored and their K = 0
-// adds nothing to dQ; queries past N carry nlse = −inf (P = 0) and dO = 0.
+// Keys past Nk are zero rows whose own rows are not stored; the dQ kernel selects their
+// scores to −inf (P = 0: with lse < −88 their exp(0 − lse) would be inf, and inf · 0 NaN);
+// queries past N carry nlse = −inf (P = 0) and dO = 0.
 // --------------------------------------------------------------------------
 constexpr int kF32T = 32;   // tile of the streamed side
 constexpr int kF32R = 33;   // LDS row (floats)
@@ -456,6 +461,7 @@ __global__ __launch_bounds__(256) void bwd_dq_f32(BwdParams p) {
             if constexpr (CAUSAL) {
                 if (k0 + acc_row(x, h) > qi + p.off) sa[x] = kNegInf;
             }
+            if (k0 + kF32T > Nk && k0 + acc_row(x, h) >= Nk) sa[x] = kNegInf;   // the ragged last tile
             const float pr = exp2f((sa[x] + nlq) * c);
             pa[x] = pr * (pa[x] + ndq);          // dSᵀ
         }
@@ -633,7 +639,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
         }
         const char* kimg = st;
         const char* vimg = st + KB;
-        const bool partial = (t + 1) * 64 > Nk;
+        const bool partial = (t + 1) * 64 > p.nkv;
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
             f32x16 sa, dp;
@@ -646,7 +652,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
             if (partial) {
 #pragma unroll
                 for (int x = 0; x < 16; ++x)
-                    if (t * 64 + kb * 32 + (x & 7) + 8 * h + 16 * (x >> 3) >= Nk) sa[x] = kNegInf;
+                    if (t * 64 + kb * 32 + (x & 7) + 8 * h + 16 * (x >> 3) >= p.nkv) sa[x] = kNegInf;
             }
             if constexpr (CAUSAL) {
                 const int w0 = wlim0 - t * 64 - kb * 32;   // ... relative to the 32-key block
@@ -1097,7 +1103,7 @@ __global__ __launch_bounds__(512, 1) void bwd_fused(BwdParams p) {
     const auto vrs = bslab<T>(p.V, (int64_t)b * Nk * DV, (int64_t)Nk * DV);
     const int key0 = j * 256;
     const int kj = key0 + 32 * wave + sig32(r);   // this lane's key (column of S, dP, dKᵀ, dVᵀ)
-    const bool key_ok = kj < Nk;
+    const bool key_ok = kj < p.nkv;   // (the padded path's zero rows: P = 0, nothing stored)
     const float c = p.scale_log2;
     const float* nlse = p.nlse + (int64_t)b * N;
     const float* nDg = p.nD + (int64_t)b * N;
@@ -1813,6 +1819,7 @@ int launch_dense_bwd(const DenseBwdArgs& a, hipStream_t s, const char** why) {
     p.nD = (float*)(w + pl.off_nD);
     p.nlse = (float*)(w + pl.off_nlse);
     p.N = (int)a.N; p.Nk = (int)a.Nk; p.d = (int)a.d; p.dv = (int)a.dv; p.batch = (int)a.batch;
+    p.nkv = (int)a.Nk;   // stays the caller's on the padded path
     p.scale = a.scale;
     p.scale_log2 = a.scale * kLog2e;
     hipError_t e;

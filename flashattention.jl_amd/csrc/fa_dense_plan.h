@@ -323,9 +323,10 @@ inline bool bwd_shape_fast(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t 
 //
 // Padded fast path: 16-bit shapes the MFMA kernels do not take directly (N or Nk not a
 // multiple of 8, d or dv not 32 / 64 / 128) are copied into zero-padded workspace slabs and
-// run on the fast kernels.  Zero keys and values are exact there: with the forward's lse they
-// add P·0 to dP and dS·0 to dQ, and their own dK / dV rows are dropped; padded queries carry
-// dO = O = 0 (so dS = 0) and l = 1, m = 0 (finite P, no NaN).  A fast shape with a misaligned
+// run on the fast kernels.  The zero keys past the caller's Nk are masked where a dQ is summed
+// (BwdParams::nkv: P = 0; left to P·0 they break once exp(0 − lse) overflows, which fp16's dS
+// does from lse < −11 on), and their own dK / dV rows are dropped; zero features add 0 to every
+// product; padded queries carry dO = O = 0 (so dS = 0) and l = 1, m = 0 (finite P, no NaN).  A fast shape with a misaligned
 // tensor is NOT padded: it runs the generic kernels.
 //
 // Single pass (bwd_fused) on the extents the fast kernels run: K = ceil(Nk/256) members per

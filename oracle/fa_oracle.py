@@ -90,12 +90,18 @@ def dense_dpa(q, k, v):
 # --------------------------------------------------------------------------
 # blockwise FA-1 forward: dense_fa!
 # --------------------------------------------------------------------------
-def dense_fa3(Q, K, V, M: int = CACHE_M):
+def _tau(scale: float, d: int) -> float:
+    """The C ABI's rule (include/fa_hip.h): ``scale <= 0`` means 1/√d."""
+    return float(scale) if scale > 0 else 1.0 / math.sqrt(d)
+
+
+def dense_fa3(Q, K, V, M: int = CACHE_M, scale: float = 0.0):
     """Blockwise forward ``dense_fa!(O, l, m, Q, K, V)`` — src/dense.jl:21-102.
 
     Same tile policy (:28-41), same per-tile FA-1 update with O kept normalised
     every step (:77-91).  Returns O (N, dv, B), l (N, 1, B), m (N, 1, B) with
-    l = Σⱼ exp(sᵢⱼ − mᵢ), m = maxⱼ sᵢⱼ, s = τ Q Kᵀ, τ = 1/√d (:43).
+    l = Σⱼ exp(sᵢⱼ − mᵢ), m = maxⱼ sᵢⱼ, s = τ Q Kᵀ, τ = 1/√d (:43); ``scale > 0``
+    replaces τ (the C ABI's argument, which the reference does not have).
 
     Generalisations (documented deviations): Nk may differ from N
     (the reference indexes K with N, :46-71), and dv may differ from d (the
@@ -109,7 +115,7 @@ def dense_fa3(Q, K, V, M: int = CACHE_M):
     dv = V.shape[1]
     Br, _ = tile_policy(N, d, M)
     _, Bc = tile_policy(Nk, d, M)
-    tau = 1.0 / math.sqrt(d)
+    tau = _tau(scale, d)
     O = np.zeros((N, dv, B))
     l = np.zeros((N, 1, B))
     m = np.full((N, 1, B), -np.inf)
@@ -162,10 +168,10 @@ def dense_fa(q, k, v, M: int = CACHE_M):
 # --------------------------------------------------------------------------
 # backward
 # --------------------------------------------------------------------------
-def dense_fa_backward(Q, K, V, O, dO, l, m, M: int = CACHE_M):
+def dense_fa_backward(Q, K, V, O, dO, l, m, M: int = CACHE_M, scale: float = 0.0):
     """Blockwise backward — executable spec ``OneDFastBack``
     src_cpp/FlashAttention.cpp:194-252 (loop :221-251, math :238-246), with
-    λ = τ = 1/√d as in the Julia intent src/dense.jl:131-162.
+    λ = τ = 1/√d as in the Julia intent src/dense.jl:131-162 (``scale > 0`` replaces τ).
 
     P = exp(τ Q Kᵀ − m)/l (:237-238); dV += Pᵀ dO (:239); dP = dO Vᵀ (:240);
     D = rowsum(dO∘O) (:241); dS = P∘(dP − D) (:242); dQ += τ dS K (:243);
@@ -185,7 +191,7 @@ def dense_fa_backward(Q, K, V, O, dO, l, m, M: int = CACHE_M):
     Nk = K.shape[0]
     l = np.asarray(l, dtype=np.float64).reshape(N, B)
     m = np.asarray(m, dtype=np.float64).reshape(N, B)
-    tau = 1.0 / math.sqrt(d)
+    tau = _tau(scale, d)
     Br, _ = tile_policy(N, d, M)
     _, Bc = tile_policy(Nk, d, M)
     dQ = np.zeros_like(Q)
@@ -284,13 +290,13 @@ def coverage(spatial: Sequence[int], ws: int, stride: int, pad: int) -> np.ndarr
 
 
 def windowed_fa(q, k, v, ws: int, stride: int | None = None, pad: int | None = None,
-                attn=None):
+                attn=None, scale: float = 0.0):
     """``windowed_fa(q, k, v, ws; stride=ws, pad=(ws-1)÷2)`` — src/windowed.jl:3-23.
 
     window q, k, v (:4-6) → dense_fa on (ws^k, d, L·B) (:8-11) → fold ÷
     coverage count (:16-19).  Pixels no window covers come out 0/0 = NaN
     (Appendix A.7; reproduced, not fixed).  Returns y (spatial..., dv, B),
-    l, m (ws^k, 1, L, B) in window layout (:20-21).
+    l, m (ws^k, 1, L, B) in window layout (:20-21).  ``scale > 0`` replaces τ = 1/√d.
     """
     stride = ws if stride is None else stride
     pad = (ws - 1) // 2 if pad is None else pad
@@ -302,7 +308,7 @@ def windowed_fa(q, k, v, ws: int, stride: int | None = None, pad: int | None = N
     dv = vw.shape[1]
     r = lambda a: np.reshape(a, (a.shape[0], a.shape[1], -1), order="F")
     if attn is None:
-        yw, lw, mw = dense_fa3(r(qw), r(kw), r(vw))
+        yw, lw, mw = dense_fa3(r(qw), r(kw), r(vw), scale=scale)
     else:
         yw, lw, mw = attn(r(qw), r(kw), r(vw))
     yw = np.reshape(yw, (T, dv, L, B), order="F")
@@ -341,7 +347,7 @@ def windowed_dpa(q, k, v, ws: int, stride: int | None = None, pad: int | None = 
 
 
 def windowed_fa_backward(q, k, v, dy, ws: int, stride: int | None = None,
-                         pad: int | None = None):
+                         pad: int | None = None, scale: float = 0.0):
     """Composed windowed backward (the reference README
     claims it, README.md:36-37, no code exists): dyw = window(dy ./ divisor),
     dense backward per window, fold(dqw/dkw/dvw).  Chain rule of
@@ -355,12 +361,12 @@ def windowed_fa_backward(q, k, v, dy, ws: int, stride: int | None = None,
     T, d, L, B = qw.shape
     dv = vw.shape[1]
     r = lambda a: np.reshape(a, (a.shape[0], a.shape[1], -1), order="F")
-    Ow, lw, mw = dense_fa3(r(qw), r(kw), r(vw))
+    Ow, lw, mw = dense_fa3(r(qw), r(kw), r(vw), scale=scale)
     div = coverage(q.shape[:-2], ws, stride, pad)
     with np.errstate(invalid="ignore", divide="ignore"):
         g = np.asarray(dy, dtype=np.float64) / div.reshape(div.shape + (1, 1))
     dyw = window(g, ws, stride, pad)
-    dQw, dKw, dVw = dense_fa_backward(r(qw), r(kw), r(vw), Ow, r(dyw), lw, mw)
+    dQw, dKw, dVw = dense_fa_backward(r(qw), r(kw), r(vw), Ow, r(dyw), lw, mw, scale=scale)
     sp = tuple(q.shape[:-2])
     dq = unwindow(np.reshape(dQw, (T, d, L, B), order="F"), sp + (d, q.shape[-1]), ws, stride, pad)
     dk = unwindow(np.reshape(dKw, (T, d, L, B), order="F"), sp + (d, q.shape[-1]), ws, stride, pad)

@@ -1,0 +1,216 @@
+"""Ill-conditioned attention inputs and a low-precision yardstick for the backward tests
+(helper for the tests, not a test).
+
+family(): five input families that leave the regime of N(0, 1) inputs at scale 1/sqrt(d)
+(unit-variance scores, row maxima of 2..5, the explicit scale argument unused):
+
+    hot      N(0, 1) q, k at scale 4/sqrt(d): peaked rows (max P about 0.45), m = 7..20
+    cold     N(0, 1) q, k at scale 0.25/sqrt(d): near-uniform P
+    offset   q, k = 0.5 N(0, 1) + 3u, default scale: every score carries the common offset
+             9 sqrt(d) (m = 70..80 at d = 64, 102..111 at d = 128; raw q.k = 600..1200)
+    anti     q = 0.5 N(0, 1) + 3u, k = 0.5 N(0, 1) - 3u: the same offset, negative
+    hotkeys  N(0, 1), then k[j] = 8 q[i] for three (i, j): those rows reach m = 8 |q_i|^2 /
+             sqrt(d), and those keys draw weight from many other rows (scores 8 q_i'.q_i / sqrt(d))
+
+u is a fixed +-1 vector of length d; v and do are N(0, 1) in every family.
+
+lowp_backward(): the backward in the kernels' FORMULATION (not their code), in numpy: float32
+raw scores, nlse = -(m + ln l) / tau in float32, P = exp2((s_raw + nlse) tau log2 e) in
+float32, dS = P (dP - D) in float32, P and dS rounded to the 16-bit type before the three
+gradient products (taken in float64).  Its distance to the float64 reference on a case is what
+the formulation itself costs there: e_ref() measures it, budget() turns it into a tolerance.
+"""
+from __future__ import annotations
+
+import math
+import zlib
+
+import numpy as np
+import torch
+
+FAMILIES = ("hot", "cold", "offset", "anti", "hotkeys")
+GTOL = {"float32": 2e-5, "bfloat16": 2e-2, "float16": 5e-3}
+ROUND16 = {"float32": None, "bfloat16": "bf16", "float16": "fp16", "float64": None}
+LOG2E = 1.4426950408889634
+
+
+def round_to(a, dtype: str) -> np.ndarray:
+    """a rounded to `dtype` (bf16 for float32 and float64, as the other tests do), as float64."""
+    t = torch.float16 if dtype == "float16" else torch.bfloat16
+    return torch.tensor(np.asarray(a, dtype=np.float64)).to(t).double().numpy()
+
+
+def _round16(a: np.ndarray, kind) -> np.ndarray:
+    if kind is None:
+        return a.astype(np.float64)
+    assert kind in ("bf16", "fp16"), kind
+    t = torch.bfloat16 if kind == "bf16" else torch.float16
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(t).double().numpy()
+
+
+def sign_vector(d: int) -> np.ndarray:
+    """The fixed +-1 vector u of length d."""
+    return np.where(np.random.default_rng(1000 + d).random(d) < 0.5, -1.0, 1.0)
+
+
+def hot_pairs(N: int, Nk: int, B: int, mask=None):
+    """Three (i, j, slab) with the keys j in different thirds of the key range (different 64-key
+    tiles from Nk = 192 up) and, at B > 1, different slabs.  With a mask ((N, Nk) bool: key j
+    is visible to query i) the query is the middle one of those that see key j."""
+    out = []
+    for t in range(min(3, Nk)):
+        j = min(Nk - 1, ((2 * t + 1) * Nk) // 6 + t)
+        if mask is None:
+            i = (j * 7 + 13 * (t + 1)) % N
+        else:
+            rows = np.flatnonzero(np.asarray(mask)[:, j])
+            assert rows.size, f"no query sees key {j}"
+            i = int(rows[rows.size // 2])
+        out.append((i, j, t % B))
+    return out
+
+
+def family(name: str, N: int, Nk: int, d: int, dv: int, B: int, dtype: str, mask=None):
+    """(q, k, v, do, scale): float64 arrays (N, d, B), (Nk, d, B), (Nk, dv, B), (N, dv, B) that
+    are exactly representable in `dtype`, and the scale argument to pass (0: the default).
+    Seeded from (name, N, Nk, d).  mask places the hotkeys pairs where query i sees key j."""
+    assert name in FAMILIES, name
+    rng = np.random.default_rng(zlib.crc32(f"{name}-{N}-{Nk}-{d}".encode()))
+    q, k = rng.standard_normal((N, d, B)), rng.standard_normal((Nk, d, B))
+    v, do = rng.standard_normal((Nk, dv, B)), rng.standard_normal((N, dv, B))
+    scale = 0.0
+    # the C ABI takes scale as a float: the value returned is the float32 the device receives
+    if name == "hot":
+        scale = float(np.float32(4.0 / math.sqrt(d)))
+    elif name == "cold":
+        scale = float(np.float32(0.25 / math.sqrt(d)))
+    elif name in ("offset", "anti"):
+        u = sign_vector(d)[None, :, None]
+        q = 0.5 * q + 3.0 * u
+        k = 0.5 * k + (3.0 if name == "offset" else -3.0) * u
+    q, k, v, do = (round_to(a, dtype) for a in (q, k, v, do))
+    if name == "hotkeys":
+        for i, j, b in hot_pairs(N, Nk, B, mask):
+            k[j, :, b] = 8.0 * q[i, :, b]        # a power of two: still representable
+    return q, k, v, do, scale
+
+
+def tau_of(scale: float, d: int) -> float:
+    return float(scale) if scale > 0 else 1.0 / math.sqrt(d)
+
+
+def forward_f64(q, k, v, scale: float = 0.0, mask=None):
+    """O (N, dv, B), l, m (N, 1, B) in float64 of (masked) softmax(tau q k^T) v; statistics over
+    the visible keys."""
+    q, k, v = (np.asarray(a, dtype=np.float64) for a in (q, k, v))
+    N, d, B = q.shape
+    tau = tau_of(scale, d)
+    o = np.empty((N, v.shape[1], B))
+    l = np.empty((N, 1, B))
+    m = np.empty((N, 1, B))
+    for b in range(B):
+        S = tau * (q[:, :, b] @ k[:, :, b].T)
+        if mask is not None:
+            S = np.where(mask, S, -np.inf)
+        mb = S.max(axis=1)
+        E = np.exp(S - mb[:, None])
+        lb = E.sum(axis=1)
+        o[:, :, b] = (E / lb[:, None]) @ v[:, :, b]
+        l[:, 0, b], m[:, 0, b] = lb, mb
+    return o, l, m
+
+
+def backward_f64(q, k, v, do, O, l, m, scale: float = 0.0, mask=None):
+    """(dQ, dK, dV) in float64 on the O, l, m that are passed in."""
+    q, k, v, do, O = (np.asarray(a, dtype=np.float64) for a in (q, k, v, do, O))
+    N, d, B = q.shape
+    tau = tau_of(scale, d)
+    l = np.asarray(l, dtype=np.float64).reshape(N, B)
+    m = np.asarray(m, dtype=np.float64).reshape(N, B)
+    dq, dk, dvv = np.zeros_like(q), np.zeros_like(k), np.zeros_like(v)
+    for b in range(B):
+        S = tau * (q[:, :, b] @ k[:, :, b].T)
+        if mask is not None:
+            S = np.where(mask, S, -np.inf)
+        P = np.exp(S - m[:, b][:, None]) / l[:, b][:, None]
+        dP = do[:, :, b] @ v[:, :, b].T
+        D = (do[:, :, b] * O[:, :, b]).sum(axis=1)
+        dS = P * (dP - D[:, None])
+        dq[:, :, b] = tau * (dS @ k[:, :, b])
+        dk[:, :, b] = tau * (dS.T @ q[:, :, b])
+        dvv[:, :, b] = P.T @ do[:, :, b]
+    return dq, dk, dvv
+
+
+def lowp_backward(q, k, v, do, O, l, m, scale, round16=None, mask=None):
+    """(dQ, dK, dV) of the kernels' formulation (module docstring).  q (N, d, B), k (Nk, d, B),
+    v (Nk, dv, B), do, O (N, dv, B), l, m (N, 1, B) or (N, B); round16: None, "bf16" or "fp16";
+    mask: optional (N, Nk) bool, key j visible to query i."""
+    f32 = np.float32
+    q, k, v, do, O = (np.asarray(a, dtype=np.float64) for a in (q, k, v, do, O))
+    N, d, B = q.shape
+    tau = f32(tau_of(scale, d))
+    tau_log2 = f32(tau * f32(LOG2E))
+    l = np.asarray(l, dtype=f32).reshape(N, B)
+    m = np.asarray(m, dtype=f32).reshape(N, B)
+    dq, dk, dvv = np.zeros_like(q), np.zeros_like(k), np.zeros_like(v)
+    for b in range(B):
+        qb, kb, vb, dob, ob = (a[:, :, b].astype(f32) for a in (q, k, v, do, O))
+        s_raw = qb @ kb.T                                           # float32
+        nlse = (-(m[:, b] + np.log(l[:, b])) / tau).astype(f32)
+        arg = ((s_raw + nlse[:, None]) * tau_log2).astype(f32)
+        if mask is not None:
+            arg = np.where(mask, arg, f32(-np.inf))
+        P = np.exp2(arg).astype(f32)
+        dP = dob @ vb.T
+        D = (dob * ob).sum(axis=1, dtype=f32)
+        dS = (P * (dP - D[:, None])).astype(f32)
+        P16, dS16 = _round16(P, round16), _round16(dS, round16)
+        dq[:, :, b] = float(tau) * (dS16 @ k[:, :, b])
+        dk[:, :, b] = float(tau) * (dS16.T @ q[:, :, b])
+        dvv[:, :, b] = P16.T @ do[:, :, b]
+    return dq, dk, dvv
+
+
+def grad_metrics(x, y, floor: float = 1e-2):
+    """The two metrics of assert_grad_close (tests/test_gpu_backward.py): max|x - y| / max|y|
+    and ||x - y|| / ||y||, each denominator floored (at `floor`, `floor` sqrt(size))."""
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    err = np.abs(x - y).max() / max(np.abs(y).max(), floor)
+    rel = np.linalg.norm(x - y) / max(np.linalg.norm(y), floor * np.sqrt(y.size))
+    return float(err), float(rel)
+
+
+def e_ref(q, k, v, do, scale, dtype: str, mask=None) -> float:
+    """What the formulation costs on this case: the larger metric, over dQ, dK, dV, of
+    lowp_backward against the float64 backward, both on the float64 forward's O (rounded to
+    `dtype`) and its l, m (rounded to float32).  Nothing here comes from a device."""
+    o, l, m = forward_f64(q, k, v, scale, mask)
+    if dtype in ("bfloat16", "float16"):
+        o = round_to(o, dtype)
+    elif dtype == "float32":
+        o = o.astype(np.float32).astype(np.float64)
+    l, m = l.astype(np.float32), m.astype(np.float32)
+    ref = backward_f64(q, k, v, do, o, l, m, scale, mask)
+    low = lowp_backward(q, k, v, do, o, l, m, scale, ROUND16[dtype], mask)
+    return max(max(grad_metrics(x, y)) for x, y in zip(low, ref))
+
+
+def budget(dtype: str, eref: float) -> float:
+    """max(GTOL, 2 e_ref): the factor 2 is for the summation order and the MFMA accumulation,
+    which lowp_backward does not model."""
+    return max(GTOL[dtype], 2.0 * eref)
+
+
+def causal_mask(N: int, Nk: int) -> np.ndarray:
+    return np.arange(Nk)[None, :] <= np.arange(N)[:, None] + (Nk - N)
+
+
+def band_mask(N: int, W: int) -> np.ndarray:
+    """Circulant band of W <= N keys (i - p + t) mod N, p = (W - 1) // 2, as a mask."""
+    assert W <= N
+    p = (W - 1) // 2
+    mk = np.zeros((N, N), dtype=bool)
+    mk[np.arange(N)[:, None], (np.arange(N)[:, None] - p + np.arange(W)[None, :]) % N] = True
+    return mk
