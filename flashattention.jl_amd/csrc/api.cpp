@@ -217,6 +217,10 @@ int fa_debug_set_circ_generic(int v) {
     return old;
 }
 
+// Not part of the public header: which kernel the calling thread's last fa_circulant_fwd
+// launched: 0 none, 1 tiled MFMA, 2 one wave per query, 3 LDS-tiled SIMT, 4 Float64 (tests).
+int fa_debug_last_circ_fwd_kernel(void) { return fa::g_circ_fwd_last_kernel; }
+
 // Not part of the public header: which kernel family the calling thread's last
 // fa_circulant_bwd launched: 0 none, 1 MFMA tiled, 2 SIMT, 3 Float64 (tests).
 int fa_debug_last_circ_bwd_kernel(void) { return fa::g_circ_bwd_last_kernel; }

@@ -36,6 +36,7 @@
 namespace fa {
 
 thread_local int g_circ_force_generic = 0;   // debug knob: 1 = one-wave-per-query kernel, 2 = LDS-tiled SIMT kernel (non-MFMA shapes)
+thread_local int g_circ_fwd_last_kernel = 0;   // 0 none, 1 tiled MFMA, 2 one wave per query, 3 LDS-tiled SIMT, 4 Float64
 
 struct CircParams {
     const void* Q;
@@ -488,6 +489,7 @@ static void launch_circ_typed(CircParams p, int64_t batch, bool fast, hipStream_
             const int Dc = head_dim_class(p.d), DVc = head_dim_class(p.dv);
             p.nqb = (p.N + 127) / 128;
             p.total_wg = (int)(p.nqb * batch);
+            g_circ_fwd_last_kernel = 1;
             switch (Dc) {
                 case 32: launch_circ_tiled<T, 32>(p, DVc, s); break;
                 case 64: launch_circ_tiled<T, 64>(p, DVc, s); break;
@@ -501,9 +503,11 @@ static void launch_circ_typed(CircParams p, int64_t batch, bool fast, hipStream_
     if (g_circ_force_generic == 1 || (g_circ_force_generic != 2 && (int64_t)(p.N + 255) / 256 * batch < 128)) {
         p.total_wg = (int)batch;   // one-wave-per-query kernel: slab count
         const int64_t waves = (int64_t)p.N * batch;
+        g_circ_fwd_last_kernel = 2;
         hipLaunchKernelGGL((circ_fwd_generic<T>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, p);
         return;
     }
+    g_circ_fwd_last_kernel = 3;
     p.total_wg = (int)((p.N + 255) / 256 * batch);
     const dim3 grid((unsigned)p.total_wg);
     const int Dc = head_dim_class(p.d), DVc = head_dim_class(p.dv);
@@ -539,6 +543,7 @@ int launch_circulant_fwd(const CircArgs& a, hipStream_t s, const char** why) {
         case FA_DTYPE_F32: launch_circ_typed<float>(p, a.batch, false, s); break;
         case FA_DTYPE_F64: {
             const int64_t waves = a.N * a.batch;
+            g_circ_fwd_last_kernel = 4;
             hipLaunchKernelGGL(circ_fwd_f64, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, p,
                                a.scale64 > 0.0 ? a.scale64 : (double)a.scale, a.batch);
             break;

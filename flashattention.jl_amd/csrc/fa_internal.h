@@ -200,6 +200,7 @@ extern thread_local int g_bwd_xcd;            // single pass: one XCD per slab w
 extern thread_local int g_win_force_composed; // windowed: forced path (a WinMode, fa_windowed.h)
 extern thread_local int g_win_bwd_grid;       // windowed: strip backward workgroups (0: one per CU)
 extern thread_local int g_circ_force_generic; // circulant: forced kernel
+extern thread_local int g_circ_fwd_last_kernel; // circulant forward: kernel of the last launch (1 tiled MFMA, 2 one wave per query, 3 LDS-tiled SIMT, 4 Float64)
 extern thread_local int g_circ_bwd_last_kernel; // circulant backward: family of the last launch (1 MFMA, 2 SIMT, 3 Float64)
 
 }  // namespace fa

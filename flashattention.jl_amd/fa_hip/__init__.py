@@ -139,6 +139,9 @@ def lib() -> ctypes.CDLL:
                                        i64, i64, i64, i64, i64, f32, vp, ctypes.c_size_t, vp]
         L.fa_debug_last_circ_bwd_kernel.restype = ctypes.c_int
         L.fa_debug_last_circ_bwd_kernel.argtypes = []
+    if hasattr(L, "fa_debug_last_circ_fwd_kernel"):
+        L.fa_debug_last_circ_fwd_kernel.restype = ctypes.c_int
+        L.fa_debug_last_circ_fwd_kernel.argtypes = []
     if hasattr(L, "fa_causal_fwd"):
         for wq in (L.fa_causal_fwd_workspace, L.fa_causal_bwd_workspace):
             wq.restype = ctypes.c_size_t

@@ -1,5 +1,5 @@
-"""Ill-conditioned attention inputs and a low-precision yardstick for the backward tests
-(helper for the tests, not a test).
+"""Ill-conditioned attention inputs and low-precision yardsticks for the backward and the
+forward tests (helper for the tests, not a test).
 
 family(): five input families that leave the regime of N(0, 1) inputs at scale 1/sqrt(d)
 (unit-variance scores, row maxima of 2..5, the explicit scale argument unused):
@@ -19,6 +19,11 @@ raw scores, nlse = -(m + ln l) / tau in float32, P = exp2((s_raw + nlse) tau log
 float32, dS = P (dP - D) in float32, P and dS rounded to the 16-bit type before the three
 gradient products (taken in float64).  Its distance to the float64 reference on a case is what
 the formulation itself costs there: e_ref() measures it, budget() turns it into a tolerance.
+
+lowp_forward(): the forward in the kernels' formulation (its docstring); fwd_shares() states an
+(O, l, m) against the float64 forward as shares of the forward tests' limits (conftest's
+assert_close and assert_lm_close, l_rtol() for l), and e_ref_fwd() is lowp_forward's shares: what
+the limits leave to a device on a case.  band_counts(): a circulant band as key counts (W > N).
 """
 from __future__ import annotations
 
@@ -27,6 +32,8 @@ import zlib
 
 import numpy as np
 import torch
+
+from conftest import TOL
 
 FAMILIES = ("hot", "cold", "offset", "anti", "hotkeys")
 GTOL = {"float32": 2e-5, "bfloat16": 2e-2, "float16": 5e-3}
@@ -70,12 +77,13 @@ def hot_pairs(N: int, Nk: int, B: int, mask=None):
     return out
 
 
-def family(name: str, N: int, Nk: int, d: int, dv: int, B: int, dtype: str, mask=None):
+def family(name: str, N: int, Nk: int, d: int, dv: int, B: int, dtype: str, mask=None, seed: int = 0):
     """(q, k, v, do, scale): float64 arrays (N, d, B), (Nk, d, B), (Nk, dv, B), (N, dv, B) that
     are exactly representable in `dtype`, and the scale argument to pass (0: the default).
-    Seeded from (name, N, Nk, d).  mask places the hotkeys pairs where query i sees key j."""
+    Seeded from (name, N, Nk, d), and from `seed` where it is not 0 (another draw of the same
+    family).  mask places the hotkeys pairs where query i sees key j."""
     assert name in FAMILIES, name
-    rng = np.random.default_rng(zlib.crc32(f"{name}-{N}-{Nk}-{d}".encode()))
+    rng = np.random.default_rng(zlib.crc32((f"{name}-{N}-{Nk}-{d}" + (f"-{seed}" if seed else "")).encode()))
     q, k = rng.standard_normal((N, d, B)), rng.standard_normal((Nk, d, B))
     v, do = rng.standard_normal((Nk, dv, B)), rng.standard_normal((N, dv, B))
     scale = 0.0
@@ -99,21 +107,27 @@ def tau_of(scale: float, d: int) -> float:
     return float(scale) if scale > 0 else 1.0 / math.sqrt(d)
 
 
-def forward_f64(q, k, v, scale: float = 0.0, mask=None):
+def forward_f64(q, k, v, scale: float = 0.0, mask=None, counts=None):
     """O (N, dv, B), l, m (N, 1, B) in float64 of (masked) softmax(tau q k^T) v; statistics over
-    the visible keys."""
+    the visible keys.  counts: optional (N, Nk) integers, how often query i takes key j (a
+    circulant band with W > N repeats keys); it replaces mask, keys with count 0 are hidden."""
     q, k, v = (np.asarray(a, dtype=np.float64) for a in (q, k, v))
     N, d, B = q.shape
     tau = tau_of(scale, d)
     o = np.empty((N, v.shape[1], B))
     l = np.empty((N, 1, B))
     m = np.empty((N, 1, B))
+    if counts is not None:
+        assert mask is None
+        mask = np.asarray(counts) > 0
     for b in range(B):
         S = tau * (q[:, :, b] @ k[:, :, b].T)
         if mask is not None:
             S = np.where(mask, S, -np.inf)
         mb = S.max(axis=1)
         E = np.exp(S - mb[:, None])
+        if counts is not None:
+            E = E * counts
         lb = E.sum(axis=1)
         o[:, :, b] = (E / lb[:, None]) @ v[:, :, b]
         l[:, 0, b], m[:, 0, b] = lb, mb
@@ -203,6 +217,94 @@ def budget(dtype: str, eref: float) -> float:
     return max(GTOL[dtype], 2.0 * eref)
 
 
+def l_rtol(m_ref, dtype: str) -> float:
+    """The limit on |l - l_ref| / (1 + |l_ref|): conftest's rule where float32 scores allow it.
+    A float32 score of size |s| moves its exponential by up to a few |s| 2^-24 (2.6e-5 at
+    |s| = 110), whatever the kernel does.  dtype names the conftest row (float32 for Float64
+    kernels: l, m leave every kernel as float32)."""
+    return max(TOL[dtype]["lm"], 8.0 * float(np.abs(m_ref).max()) * 2.0 ** -24)
+
+
+def lowp_forward(q, k, v, scale, round16=None, mask=None, counts=None, lag_log2: float = 0.0):
+    """(O, l, m) of the forward kernels' FORMULATION (not their code), in numpy: float32 raw
+    scores s, c = tau log2(e) in float32, P = exp2(fma(s, c, -m_used c)) in float32 with m_used
+    lag_log2 / c below the row maximum (the lazy rescale lets it lag by up to 8 log2 units), l
+    summed in float32, P rounded to the 16-bit type before P V (taken in float64), O rounded
+    to the output type (float32 where round16 is None), l = l_used 2^((m_used - m) c),
+    m = max(s) tau.  mask, counts as in forward_f64 (a repeated key adds its rounded P each time)."""
+    f32 = np.float32
+    q, k, v = (np.asarray(a, dtype=np.float64) for a in (q, k, v))
+    N, d, B = q.shape
+    tau = f32(tau_of(scale, d))
+    c = f32(tau * f32(LOG2E))
+    if counts is not None:
+        assert mask is None
+        counts = np.asarray(counts)
+        mask = counts > 0
+    o = np.empty((N, v.shape[1], B))
+    l = np.empty((N, 1, B))
+    m = np.empty((N, 1, B))
+    for b in range(B):
+        s_raw = q[:, :, b].astype(f32) @ k[:, :, b].astype(f32).T
+        if mask is not None:
+            s_raw = np.where(mask, s_raw, f32(-np.inf))
+        m_true = s_raw.max(axis=1)
+        m_used = (m_true - f32(lag_log2) / c).astype(f32)
+        mc = (m_used * c).astype(f32)
+        arg = (s_raw.astype(np.float64) * float(c) - mc.astype(np.float64)[:, None]).astype(f32)   # one rounding: the fma
+        P = np.exp2(arg).astype(f32)
+        P16 = _round16(P, round16)
+        if counts is not None:
+            P, P16 = (P * counts).astype(f32), P16 * counts
+        l_used = P.sum(axis=1, dtype=f32)
+        ob = (P16 @ v[:, :, b]) / l_used.astype(np.float64)[:, None]
+        o[:, :, b] = ob.astype(f32) if round16 is None else _round16(ob, round16)
+        l[:, 0, b] = (l_used * np.exp2(((m_used - m_true) * c).astype(f32))).astype(f32)
+        m[:, 0, b] = (m_true * tau).astype(f32)
+    return o, l, m
+
+
+ELEM64 = 1e-12   # Float64 outputs: relative to max(|y|, 1) (tests/test_gpu_float64.py)
+
+
+def fwd_shares(o, l, m, o_ref, l_ref, m_ref, dtype: str) -> dict:
+    """What share of each forward limit (o, l, m) uses against the float64 (o_ref, l_ref,
+    m_ref): conftest.assert_close's norm-wise and elementwise limits on O (Float64: ELEM64),
+    assert_lm_close's on m, l_rtol on l.  A share above 1 fails the assertion it stands for."""
+    x, y = np.asarray(o, dtype=np.float64), np.asarray(o_ref, dtype=np.float64)
+    err = np.abs(x - y)
+    out = {}
+    if dtype == "float64":
+        out["O elem"] = err.max() / max(np.abs(y).max(), 1.0) / ELEM64
+        lm_dt = "float32"
+    else:
+        t = TOL[dtype]
+        lm_dt = dtype
+        out["O norm"] = np.linalg.norm(x - y) / (t["norm"] * max(np.linalg.norm(x), np.linalg.norm(y), 1e-30))
+        if dtype == "float32":
+            out["O elem"] = err.max() / (t["elem_rel_max"] * np.abs(y).max() + t["elem_abs"])
+        else:
+            out["O elem"] = (err / (t["elem"] * (1 + np.abs(y)))).max()
+    rel = lambda a, r: (np.abs(np.asarray(a, dtype=np.float64) - r) / (1 + np.abs(r))).max()
+    out["l"] = rel(l, l_ref) / l_rtol(m_ref, lm_dt)
+    out["m"] = rel(m, m_ref) / TOL[lm_dt]["lm"]
+    return {nm: float(s) for nm, s in out.items()}
+
+
+def e_ref_fwd(q, k, v, scale, dtype: str, mask=None, counts=None, ref=None) -> dict:
+    """What the forward formulation costs on this case: fwd_shares of lowp_forward against the
+    float64 forward (ref, if the caller has it), per limit the worse of no lag and a lag of 8
+    log2 units.  Nothing here comes from a device.  Float64: the reference itself, all 0."""
+    ref = forward_f64(q, k, v, scale, mask, counts) if ref is None else ref
+    if dtype == "float64":
+        return dict.fromkeys(("O elem", "l", "m"), 0.0)
+    worst = {}
+    for lag in (0.0, 8.0):
+        sh = fwd_shares(*lowp_forward(q, k, v, scale, ROUND16[dtype], mask, counts, lag), *ref, dtype)
+        worst = {nm: max(s, worst.get(nm, 0.0)) for nm, s in sh.items()}
+    return worst
+
+
 def causal_mask(N: int, Nk: int) -> np.ndarray:
     return np.arange(Nk)[None, :] <= np.arange(N)[:, None] + (Nk - N)
 
@@ -214,3 +316,13 @@ def band_mask(N: int, W: int) -> np.ndarray:
     mk = np.zeros((N, N), dtype=bool)
     mk[np.arange(N)[:, None], (np.arange(N)[:, None] - p + np.arange(W)[None, :]) % N] = True
     return mk
+
+
+def band_counts(N: int, W: int) -> np.ndarray:
+    """(N, N) integers: how often the band (i - p + t) mod N, t < W, p = (W - 1) // 2, of query
+    i takes key j.  W <= N: band_mask as 0 / 1; W > N: the keys repeat."""
+    p = (W - 1) // 2
+    cnt = np.zeros((N, N), dtype=np.int64)
+    rows = np.broadcast_to(np.arange(N)[:, None], (N, W))
+    np.add.at(cnt, (rows, (np.arange(N)[:, None] - p + np.arange(W)[None, :]) % N), 1)
+    return cnt

@@ -128,6 +128,68 @@ def test_helper_references_agree_with_the_oracle():
         assert np.abs(x - y).max() <= 1e-12 * max(np.abs(y).max(), 1.0)
 
 
+# ---- the forward yardstick (tests/test_gpu_forward_conditioning.py) --------------------------
+def _forward_rows():
+    """Every (entry, shape, dtype) of the GPU table once (the yardstick does not depend on the
+    route), Float64 aside: there the reference is its own yardstick."""
+    import test_gpu_forward_conditioning as G
+    rows = sorted({(e, s, dt) for e, _, s, dts in G.ROUTES for dt in dts if dt != "float64"})
+    return [pytest.param(e, s, dt, name, id=f"{e}-{G._sid(s)}-{dt}-{name}") for e, s, dt in rows for name in C.FAMILIES]
+
+
+@pytest.mark.parametrize("entry,shape,dtype,name", _forward_rows())
+def test_forward_formulation_leaves_headroom(entry, shape, dtype, name):
+    """The condition on the inputs of the GPU forward cases, checked before any GPU run: the
+    kernels' formulation alone (lowp_forward, with m_used at and 8 log2 units below the row
+    maximum) uses at most half of each limit that the GPU test applies (O norm-wise and
+    elementwise, l, m), on the slabs that test checks.  A case above 0.5 needs another shape or
+    seed, not another limit."""
+    import test_gpu_forward_conditioning as G
+    eref = G.case(entry, G.resolve(shape, G.MI355X_CUS), dtype, name)[5]
+    print(f"{entry} {G._sid(shape)} {dtype} {name}: " + ", ".join(f"{nm} {s:.3f}" for nm, s in eref.items()))
+    assert max(eref.values()) <= 0.5, eref
+
+
+@pytest.mark.parametrize("lag", [0.0, 8.0])
+def test_lowp_forward_mask_is_a_restriction_to_the_visible_keys(lag):
+    """lowp_forward with a mask (or counts of 0 / 1) gives each row what the unmasked call gives
+    on that row's visible keys alone (float32 scores: equal up to the summation order)."""
+    q, k, v, _, scale = C.family("hot", 40, 56, 16, 8, 2, "bfloat16")
+    close = lambda x, y: np.abs(x - y).max() <= 1e-5 * max(np.abs(y).max(), 1.0)
+    for mk in (C.causal_mask(40, 56), C.band_mask(40, 9)):
+        kk, vv = (k, v) if mk.shape[1] == 56 else (k[:40], v[:40])
+        full = C.lowp_forward(q, kk, vv, scale, None, mk, lag_log2=lag)
+        same = C.lowp_forward(q, kk, vv, scale, None, counts=mk.astype(np.int64), lag_log2=lag)
+        for x, y in zip(full, same):
+            assert np.array_equal(x, y)
+        for i in (0, 7, 39):
+            vis = np.flatnonzero(mk[i])
+            row = C.lowp_forward(q[i:i + 1], kk[vis], vv[vis], scale, None, lag_log2=lag)
+            for x, y in zip(row, full):
+                assert close(x, y[i:i + 1])
+    # and the model is the float64 forward up to float32 rounding
+    for x, y in zip(C.lowp_forward(q, k, v, scale, None, lag_log2=lag), C.forward_f64(q, k, v, scale)):
+        assert np.abs(x - y).max() <= 1e-4 * max(np.abs(y).max(), 1.0)
+
+
+@pytest.mark.parametrize("N,W", [(40, 9), (40, 40), (12, 30), (7, 15), (30, 7)])
+def test_band_counts_agree_with_the_oracle(N, W):
+    """band_counts against the reference's own band index (oracle.circulant_index), against
+    band_mask where W <= N, and, through forward_f64(counts=), against circulant_fa3."""
+    cnt = C.band_counts(N, W)
+    J = O.circulant_index(N, W)                       # (W, N)
+    want = np.zeros((N, N), dtype=np.int64)
+    np.add.at(want, (np.broadcast_to(np.arange(N)[None, :], (W, N)), J), 1)
+    assert np.array_equal(cnt, want) and np.all(cnt.sum(axis=1) == W)
+    if W <= N:
+        assert np.array_equal(cnt, C.band_mask(N, W).astype(np.int64))
+    else:
+        assert cnt.max() >= 2 and cnt.min() >= 1
+    q, k, v, _, _ = C.family("hotkeys", N, N, 16, 8, 2, "bfloat16", mask=cnt > 0)
+    for x, y in zip(C.forward_f64(q, k, v, 0.0, counts=cnt), O.circulant_fa3(q, k, v, W)):
+        assert np.abs(x - y).max() <= 1e-12 * max(np.abs(y).max(), 1.0)
+
+
 def test_hot_pairs_follow_the_mask():
     for mk in (C.causal_mask(200, 328), C.band_mask(136, 33)):
         for i, j, b in C.hot_pairs(mk.shape[0], mk.shape[1], 2, mk):

@@ -28,7 +28,7 @@ import torch
 import cond_inputs as C
 from causal_ref import causal_bwd_ref
 from circ_bwd_ref import circulant_bwd_ref
-from conftest import TOL, assert_lm_close
+from conftest import assert_lm_close
 from oracle import fa_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -197,9 +197,8 @@ def test_backward_route_under_family(fa, entry, route, shape, dtype, name):
     _, lr, mr = C.forward_f64(q, k, v, scale, mask)
     lm_dt = F32 if dtype == F64T else dtype      # l, m leave every kernel as float32
     assert_lm_close(_np(m), mr, lm_dt, "m")
-    # l at conftest's rule where float32 scores allow it: a float32 score of size |s| moves its
-    # exponential by up to a few |s| 2^-24 (2.6e-5 at |s| = 110), whatever the kernel does
-    l_rtol = max(TOL[lm_dt]["lm"], 8.0 * np.abs(mr).max() * 2.0 ** -24)
+    # l at conftest's rule where float32 scores allow it (cond_inputs.l_rtol)
+    l_rtol = C.l_rtol(mr, lm_dt)
     l_err = (np.abs(_np(l) - lr) / (1 + np.abs(lr))).max()
     assert l_err <= l_rtol, f"l: rel err {l_err:.3e} > {l_rtol:.1e}"
     ref = reference(entry, shape, dtype, q, k, v, do, scale, _np(Oo), _np(l), _np(m))
