@@ -271,7 +271,7 @@ int fa_debug_dense_fwd_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t
                             int variant, int causal_order, int kv_aligned16, int qo_aligned16, size_t ws_bytes,
                             int cus, int64_t* out) {
     if (!valid_dtype(dtype) || N < 1 || Nk < 1 || d < 1 || dv < 1 || batch < 1 || (causal && Nk < N)) return -1;
-    const fa::DenseFwdPlan pl = fa::dense_fwd_plan(dtype, N, Nk, d, dv, batch, causal != 0, {variant, causal_order},
+    const fa::DenseFwdPlan pl = fa::dense_fwd_plan(dtype, N, Nk, d, dv, batch, fa::dense_mask(causal, 0), {variant, causal_order},
                                                    kv_aligned16 != 0, qo_aligned16 != 0, ws_bytes, cus);
     if (out) {
         const int64_t f[17] = {pl.causal, pl.pad, pl.ldk, pl.nsplit, pl.tps, pl.rows, pl.nqb, pl.total_wg, pl.grid,
@@ -289,7 +289,7 @@ int fa_debug_dense_bwd_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t
     if (!valid_dtype(dtype) || N < 1 || Nk < 1 || d < 1 || dv < 1 || batch < 1 || (causal && Nk < N) ||
         d > fa::kMaxHeadDim || dv > fa::kMaxHeadDim)
         return -1;
-    const fa::DenseBwdPlan pl = fa::dense_bwd_plan(dtype, N, Nk, d, dv, batch, causal != 0,
+    const fa::DenseBwdPlan pl = fa::dense_bwd_plan(dtype, N, Nk, d, dv, batch, fa::dense_mask(causal, 0),
                                                    {force_generic, mode, hoff, xcd}, qkvdo_aligned16 != 0, ws_bytes, cus);
     if (out) {
         int64_t* o = out;
@@ -486,6 +486,113 @@ int fa_causal_bwd(int dtype, const void* Q, const void* K, const void* V, const 
     a.causal = 1;
     rc = fa::launch_dense_bwd(a, (hipStream_t)hip_stream, &why);
     return rc == FA_OK ? ok() : fail(rc, fn, why);
+}
+
+// fa_local_fwd / fa_local_bwd: the causal pair's contract (the same checks in the same order,
+// the same workspace totals) with the window (left, right) around the causal diagonal.  The
+// window stays int64_t down to the launchers, which clamp it to [0, Nk] (fa::local_clamp)
+// before it becomes a 32-bit int; it changes neither a check nor a workspace answer.
+static int local_shape_check(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, bool bwd,
+                             const char** why) {
+    if (d <= fa::kMaxHeadDim && dv <= fa::kMaxHeadDim && Nk < N) {
+        *why = "local attention needs Nk >= N (a query would see no key)";
+        return FA_ERR_UNSUPPORTED;
+    }
+    return causal_shape_check(dtype, N, Nk, d, dv, batch, bwd, why);
+}
+
+size_t fa_local_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
+    if (!valid_dtype(dtype) || N < 1 || Nk < N || d < 1 || dv < 1 || batch < 1) return 0;
+    return fa::local_fwd_workspace(dtype, N, Nk, d, dv, batch);
+}
+
+int fa_local_fwd(int dtype, const void* Q, const void* K, const void* V, void* O, float* l, float* m,
+                 int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, int64_t left, int64_t right,
+                 float scale, void* workspace, size_t workspace_bytes, void* hip_stream) {
+    static const char* fn = "fa_local_fwd";
+    if (!valid_dtype(dtype)) return fail(FA_ERR_INVALID_ARG, fn, "unknown dtype");
+    if (N < 0 || Nk < 0 || d < 1 || dv < 1 || batch < 0)
+        return fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: N, Nk, batch must be >= 0 and d, dv >= 1");
+    if (N == 0 || batch == 0) return ok();   // no query: nothing to write
+    if (!Q || !K || !V || !O || !l || !m) return fail(FA_ERR_INVALID_ARG, fn, "null pointer");
+    const char* why = "";
+    int rc = local_shape_check(dtype, N, Nk, d, dv, batch, false, &why);
+    if (rc != FA_OK) return fail(rc, fn, why);
+    const size_t need = fa::local_fwd_workspace(dtype, N, Nk, d, dv, batch);
+    if (need > 0 && (!workspace || workspace_bytes < need))
+        return fail(FA_ERR_WORKSPACE, fn, "workspace missing or smaller than fa_local_fwd_workspace()");
+    fa::DenseArgs a{dtype, Q, K, V, O, l, m, N, Nk, d, dv, batch, resolve_scale(scale, d)};
+    a.scale64 = resolve_scale64(scale, d);
+    a.workspace = workspace;
+    a.workspace_bytes = workspace_bytes;
+    a.local = 1;
+    a.left = left;
+    a.right = right;
+    rc = fa::launch_dense_fwd(a, (hipStream_t)hip_stream, &why);
+    return rc == FA_OK ? ok() : fail(rc, fn, why);
+}
+
+size_t fa_local_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
+    if (!valid_dtype(dtype) || N < 1 || Nk < N || d < 1 || dv < 1 || batch < 1) return 0;
+    return fa::local_bwd_workspace(dtype, N, Nk, d, dv, batch);
+}
+
+int fa_local_bwd(int dtype, const void* Q, const void* K, const void* V, const void* O, const void* dO,
+                 const float* l, const float* m, void* dQ, void* dK, void* dV, int64_t N, int64_t Nk,
+                 int64_t d, int64_t dv, int64_t batch, int64_t left, int64_t right, float scale,
+                 void* workspace, size_t workspace_bytes, void* hip_stream) {
+    static const char* fn = "fa_local_bwd";
+    if (!valid_dtype(dtype)) return fail(FA_ERR_INVALID_ARG, fn, "unknown dtype");
+    if (N < 0 || Nk < 0 || d < 1 || dv < 1 || batch < 0)
+        return fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: N, Nk, batch must be >= 0 and d, dv >= 1");
+    if (N == 0 || batch == 0) return ok();   // no query (and, with Nk >= N required, no call with keys only)
+    if (!Q || !K || !V || !O || !dO || !l || !m || !dQ || !dK || !dV)
+        return fail(FA_ERR_INVALID_ARG, fn, "null pointer");
+    const char* why = "";
+    int rc = local_shape_check(dtype, N, Nk, d, dv, batch, true, &why);
+    if (rc != FA_OK) return fail(rc, fn, why);
+    const size_t need = fa::local_bwd_workspace(dtype, N, Nk, d, dv, batch);
+    if (!workspace || workspace_bytes < need)
+        return fail(FA_ERR_WORKSPACE, fn, "workspace missing or smaller than fa_local_bwd_workspace()");
+    fa::DenseBwdArgs a{dtype, Q, K, V, O, dO, l, m, dQ, dK, dV, N, Nk, d, dv, batch,
+                       resolve_scale(scale, d), workspace, workspace_bytes};
+    a.scale64 = resolve_scale64(scale, d);
+    a.local = 1;
+    a.left = left;
+    a.right = right;
+    rc = fa::launch_dense_bwd(a, (hipStream_t)hip_stream, &why);
+    return rc == FA_OK ? ok() : fail(rc, fn, why);
+}
+
+// Not part of the public header (tests): the plans of a local call, as fa_debug_dense_fwd_plan /
+// fa_debug_dense_bwd_plan give the dense and causal ones (those hooks keep their signatures).
+// Returns the kernel family (a fa::DenseFwdKernel / fa::DenseBwdKernel; -1: invalid arguments).
+// The window is not an argument: no plan depends on it.  Planned under the default knobs.
+// forward out[8]: local, causal bits, pad, ldk, nsplit, rows, grid, total; backward out[6]:
+// padded, N, Nk, d, dv as run, total.
+int fa_debug_local_fwd_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch,
+                            int kv_aligned16, int qo_aligned16, size_t ws_bytes, int cus, int64_t* out) {
+    if (!valid_dtype(dtype) || N < 1 || Nk < N || d < 1 || dv < 1 || batch < 1) return -1;
+    const fa::DenseFwdPlan pl = fa::dense_fwd_plan(dtype, N, Nk, d, dv, batch, fa::kMaskLocal, {fa::kFwdAuto, 0},
+                                                   kv_aligned16 != 0, qo_aligned16 != 0, ws_bytes, cus);
+    if (out) {
+        const int64_t f[8] = {pl.local, pl.causal, pl.pad, pl.ldk, pl.nsplit, pl.rows, pl.grid, (int64_t)pl.total};
+        for (int i = 0; i < 8; ++i) out[i] = f[i];
+    }
+    return pl.kernel;
+}
+int fa_debug_local_bwd_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch,
+                            int qkvdo_aligned16, size_t ws_bytes, int cus, int64_t* out) {
+    if (!valid_dtype(dtype) || N < 1 || Nk < N || d < 1 || dv < 1 || batch < 1 || d > fa::kMaxHeadDim ||
+        dv > fa::kMaxHeadDim)
+        return -1;
+    const fa::DenseBwdPlan pl = fa::dense_bwd_plan(dtype, N, Nk, d, dv, batch, fa::kMaskLocal,
+                                                   {0, fa::kBwdAuto, 3, -1}, qkvdo_aligned16 != 0, ws_bytes, cus);
+    if (out) {
+        const int64_t f[6] = {pl.padded, pl.N, pl.Nk, pl.d, pl.dv, (int64_t)pl.total};
+        for (int i = 0; i < 6; ++i) out[i] = f[i];
+    }
+    return pl.kernel;
 }
 
 int fa_dense_bwd_handoff_status(const void* workspace, size_t workspace_bytes, void* hip_stream, int* status) {

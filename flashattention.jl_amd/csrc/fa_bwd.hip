@@ -73,6 +73,10 @@ struct BwdParams {
     // j <= i + off, off = Nk - N of the caller's extents (the padded path rounds N and Nk up
     // separately and keeps this off)
     int causal = 0, off = 0;
+    // local (fa_local_bwd; read by the LOCAL instantiations only, which also read off): query i
+    // sees keys i + off - left <= j <= i + off + right, both sides clamped to [0, Nk] of the
+    // caller's extents, where Nk binds nowhere (local_clamp)
+    int local = 0, left = 0, right = 0;
 };
 
 constexpr unsigned kBwdHdrMagic = 0x46414200u;   // "FAB\0"
@@ -127,7 +131,7 @@ constexpr int kGT = 32;          // tile edge
 constexpr int kGThreads = 256;
 
 // dQ: one block per (b, 32-query tile).
-template <class T, class A, bool CAUSAL = false>
+template <class T, class A, bool CAUSAL = false, bool LOCAL = false>
 __global__ __launch_bounds__(kGThreads) void bwd_generic_dq(BwdParams p) {
     extern __shared__ __attribute__((aligned(16))) char gsm_raw[];
     A* const gsm = (A*)gsm_raw;
@@ -162,7 +166,12 @@ __global__ __launch_bounds__(kGThreads) void bwd_generic_dq(BwdParams p) {
     const A sl2 = scale_log2_a<A>(p.scale_log2, p.scale64);
     int kend = Nk;   // causal: keys up to the tile's last real query's limit
     if constexpr (CAUSAL) kend = min(Nk, min(q0 + kGT - 1, N - 1) + p.off + 1);
-    for (int k0 = 0; k0 < kend; k0 += kGT) {
+    int kbeg = 0;    // local: from the tile's first query's left edge to its last real query's right edge
+    if constexpr (LOCAL) {
+        kbeg = max(0, q0 + p.off - p.left) / kGT * kGT;
+        kend = min(Nk, min(q0 + kGT - 1, N - 1) + p.off + p.right + 1);
+    }
+    for (int k0 = kbeg; k0 < kend; k0 += kGT) {
         __syncthreads();
         for (int i = tid; i < kGT * d; i += kGThreads) {
             const int k = i % kGT, f = i / kGT;
@@ -178,6 +187,7 @@ __global__ __launch_bounds__(kGThreads) void bwd_generic_dq(BwdParams p) {
             A ds = (A)0;
             bool vis = q0 + q < N && k0 + k < Nk;
             if constexpr (CAUSAL) vis = vis && k0 + k <= q0 + q + p.off;
+            if constexpr (LOCAL) vis = vis && k0 + k <= q0 + q + p.off + p.right && k0 + k >= q0 + q + p.off - p.left;
             if (vis) {
                 A s = (A)0, dp = (A)0;
                 for (int f = 0; f < d; ++f) s = fma_a(sQ[q * ld + f], sK[k * ld + f], s);
@@ -208,7 +218,7 @@ __global__ __launch_bounds__(kGThreads) void bwd_generic_dq(BwdParams p) {
 }
 
 // dK, dV: one block per (b, 32-key tile).
-template <class T, class A, bool CAUSAL = false>
+template <class T, class A, bool CAUSAL = false, bool LOCAL = false>
 __global__ __launch_bounds__(kGThreads) void bwd_generic_dkdv(BwdParams p) {
     extern __shared__ __attribute__((aligned(16))) char gsm_raw[];
     A* const gsm = (A*)gsm_raw;
@@ -243,7 +253,14 @@ __global__ __launch_bounds__(kGThreads) void bwd_generic_dkdv(BwdParams p) {
     const A sl2 = scale_log2_a<A>(p.scale_log2, p.scale64);
     int qbeg = 0;   // causal: the first query tile that sees the block's first key
     if constexpr (CAUSAL) qbeg = max(0, k0 - p.off) / kGT * kGT;
-    for (int q0 = qbeg; q0 < N; q0 += kGT) {
+    // local: the queries i that see some key of the tile, k0 - off - right <= i <= k0 + 31 - off + left;
+    // none for keys left of every window (the loop then runs no step and zeros are stored)
+    int qend = N;
+    if constexpr (LOCAL) {
+        qbeg = max(0, k0 - p.off - p.right) / kGT * kGT;
+        qend = min(N, k0 + kGT - 1 - p.off + p.left + 1);
+    }
+    for (int q0 = qbeg; q0 < qend; q0 += kGT) {
         __syncthreads();
         for (int i = tid; i < kGT * d; i += kGThreads) {
             const int q = i % kGT, f = i / kGT;
@@ -259,6 +276,7 @@ __global__ __launch_bounds__(kGThreads) void bwd_generic_dkdv(BwdParams p) {
             A pr = (A)0, ds = (A)0;
             bool vis = q0 + q < N && k0 + k < Nk;
             if constexpr (CAUSAL) vis = vis && k0 + k <= q0 + q + p.off;
+            if constexpr (LOCAL) vis = vis && k0 + k <= q0 + q + p.off + p.right && k0 + k >= q0 + q + p.off - p.left;
             if (vis) {
                 A s = (A)0, dp = (A)0;
                 for (int f = 0; f < d; ++f) s = fma_a(sQ[q * ld + f], sK[k * ld + f], s);
@@ -317,7 +335,7 @@ __global__ __launch_bounds__(kGThreads) void bwd_generic_dkdv(BwdParams p) {
 constexpr int kF32T = 32;   // tile of the streamed side
 constexpr int kF32R = 33;   // LDS row (floats)
 
-template <int D, int DV, bool CAUSAL = false>
+template <int D, int DV, bool CAUSAL = false, bool LOCAL = false>
 __global__ __launch_bounds__(256) void bwd_dkdv_f32(BwdParams p) {
     __shared__ float sQ[D * kF32R], sdO[DV * kF32R], sL[kF32T], sD[kF32T];
     const int N = p.N, Nk = p.Nk, d = p.d, dv = p.dv;
@@ -348,7 +366,12 @@ __global__ __launch_bounds__(256) void bwd_dkdv_f32(BwdParams p) {
     const float* nL = p.nlse + (int64_t)b * N;
     int qbeg = 0;   // causal: the first query tile that sees the block's first key
     if constexpr (CAUSAL) qbeg = max(0, k0 - p.off) / kF32T * kF32T;
-    for (int q0 = qbeg; q0 < N; q0 += kF32T) {
+    int qend = N;   // local: the queries that see some key of the block (none: zeros are stored)
+    if constexpr (LOCAL) {
+        qbeg = max(0, k0 - p.off - p.right) / kF32T * kF32T;
+        qend = min(N, k0 + 127 - p.off + p.left + 1);
+    }
+    for (int q0 = qbeg; q0 < qend; q0 += kF32T) {
         __syncthreads();
         for (int i = tid; i < D * kF32T; i += 256) {
             const int q = i % kF32T, f = i / kF32T;
@@ -376,6 +399,9 @@ __global__ __launch_bounds__(256) void bwd_dkdv_f32(BwdParams p) {
             const int q = acc_row(x, h);
             if constexpr (CAUSAL) {              // select after the chain: P = exp2(-inf) = 0
                 if (key > q0 + q + p.off) sa[x] = kNegInf;
+            }
+            if constexpr (LOCAL) {
+                if (key > q0 + q + p.off + p.right || key < q0 + q + p.off - p.left) sa[x] = kNegInf;
             }
             const float pr = exp2f((sa[x] + sL[q]) * c);
             sa[x] = pr;                          // P
@@ -410,7 +436,7 @@ __global__ __launch_bounds__(256) void bwd_dkdv_f32(BwdParams p) {
     }
 }
 
-template <int D, int DV, bool CAUSAL = false>
+template <int D, int DV, bool CAUSAL = false, bool LOCAL = false>
 __global__ __launch_bounds__(256) void bwd_dq_f32(BwdParams p) {
     __shared__ float sK[D * kF32R], sV[DV * kF32R];
     const int N = p.N, Nk = p.Nk, d = p.d, dv = p.dv;
@@ -437,7 +463,12 @@ __global__ __launch_bounds__(256) void bwd_dq_f32(BwdParams p) {
         for (int x = 0; x < 16; ++x) aQ[i][x] = 0.0f;
     int kend = Nk;   // causal: keys up to the block's last real query's limit
     if constexpr (CAUSAL) kend = min(Nk, min(q0 + 127, N - 1) + p.off + 1);
-    for (int k0 = 0; k0 < kend; k0 += kF32T) {
+    int kbeg = 0;   // local: from the block's first query's left edge to its last real query's right edge
+    if constexpr (LOCAL) {
+        kbeg = max(0, q0 + p.off - p.left) / kF32T * kF32T;
+        kend = min(Nk, min(q0 + 127, N - 1) + p.off + p.right + 1);
+    }
+    for (int k0 = kbeg; k0 < kend; k0 += kF32T) {
         __syncthreads();
         for (int i = tid; i < D * kF32T; i += 256) {
             const int k = i % kF32T, f = i / kF32T;
@@ -460,6 +491,9 @@ __global__ __launch_bounds__(256) void bwd_dq_f32(BwdParams p) {
         for (int x = 0; x < 16; ++x) {
             if constexpr (CAUSAL) {
                 if (k0 + acc_row(x, h) > qi + p.off) sa[x] = kNegInf;
+            }
+            if constexpr (LOCAL) {
+                if (k0 + acc_row(x, h) > qi + p.off + p.right || k0 + acc_row(x, h) < qi + p.off - p.left) sa[x] = kNegInf;
             }
             if (k0 + kF32T > Nk && k0 + acc_row(x, h) >= Nk) sa[x] = kNegInf;   // the ragged last tile
             const float pr = exp2f((sa[x] + nlq) * c);
@@ -487,8 +521,10 @@ __global__ __launch_bounds__(256) void bwd_dq_f32(BwdParams p) {
 template <int D, int DV>
 static hipError_t launch_f32_dd(const BwdParams& p, hipStream_t s) {
     const int64_t nq = ((int64_t)p.N + 127) / 128 * p.batch, nk = ((int64_t)p.Nk + 127) / 128 * p.batch;
-    void (*dq)(BwdParams) = p.causal ? bwd_dq_f32<D, DV, true> : bwd_dq_f32<D, DV>;
-    void (*dkdv)(BwdParams) = p.causal ? bwd_dkdv_f32<D, DV, true> : bwd_dkdv_f32<D, DV>;
+    void (*dq)(BwdParams) = p.local ? bwd_dq_f32<D, DV, false, true> : p.causal ? bwd_dq_f32<D, DV, true> : bwd_dq_f32<D, DV>;
+    void (*dkdv)(BwdParams) = p.local    ? bwd_dkdv_f32<D, DV, false, true>
+                              : p.causal ? bwd_dkdv_f32<D, DV, true>
+                                         : bwd_dkdv_f32<D, DV>;
     hipLaunchKernelGGL(dq, dim3((unsigned)nq), dim3(256), 0, s, p);
     hipLaunchKernelGGL(dkdv, dim3((unsigned)nk), dim3(256), 0, s, p);
     return hipGetLastError();
@@ -580,7 +616,11 @@ __device__ void fused_combine(const BwdParams& p, int b, int qb) {
 // CAUSAL (fa_causal_bwd, never after bwd_fused: no guard, no combine): the key tiles end at
 // the block's last query's last visible tile, a wave skips the tiles past its own last query,
 // and S is selected to -inf on the tiles that straddle the wave's diagonal.
-template <class T, int D, int DV, bool CAUSAL = false>
+//
+// LOCAL (fa_local_bwd, likewise never after bwd_fused): the key tiles run from the block's first
+// query's left edge to its last query's right edge, a wave skips the tiles wholly outside
+// its own band, and S is selected to -inf on the tiles that straddle either of its diagonals.
+template <class T, int D, int DV, bool CAUSAL = false, bool LOCAL = false>
 __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
     typedef typename Frag8<T>::type F8;
     constexpr int KB = D * 128, VB = DV * 128, STAGE = KB + VB;
@@ -632,10 +672,13 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
         dma_image<DV>(vrs, st + KB, Nk, t * 64, wave, lane);
     };
     int wlim0 = 0;   // causal: the key limit (query row + off) of the wave's first query, a scalar
-    if constexpr (CAUSAL) wlim0 = qb * 128 + __builtin_amdgcn_readfirstlane(wave) * 32 + p.off;
+    if constexpr (CAUSAL || LOCAL) wlim0 = qb * 128 + __builtin_amdgcn_readfirstlane(wave) * 32 + p.off;
     auto compute = [&](const char* st, int t) {
         if constexpr (CAUSAL) {
             if (t * 64 > wlim0 + 31) return;   // wave-uniform: no query of the wave sees the tile
+        }
+        if constexpr (LOCAL) {   // ... on either side
+            if (t * 64 > wlim0 + 31 + p.right || t * 64 + 63 < wlim0 - p.left) return;
         }
         const char* kimg = st;
         const char* vimg = st + KB;
@@ -663,6 +706,22 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
                         if ((x & 7) + 16 * (x >> 3) > lr) sa[x] = kNegInf;
                 }
             }
+            if constexpr (LOCAL) {
+                // wr, wl: the right and left key limits of the wave's first query, relative to the 32-key block
+                const int wr = wlim0 + p.right - t * 64 - kb * 32, wl = wlim0 - p.left - t * 64 - kb * 32;
+                if (31 > wr) {           // a key past the first query's right limit
+                    const int lr = r - 8 * h + wr;
+#pragma unroll
+                    for (int x = 0; x < 16; ++x)
+                        if ((x & 7) + 16 * (x >> 3) > lr) sa[x] = kNegInf;
+                }
+                if (wl + 31 > 0) {       // a key before the last query's left limit
+                    const int ll = r - 8 * h + wl;
+#pragma unroll
+                    for (int x = 0; x < 16; ++x)
+                        if ((x & 7) + 16 * (x >> 3) < ll) sa[x] = kNegInf;
+                }
+            }
             F8 dsf[2];
 #pragma unroll
             for (int x = 0; x < 16; ++x) {
@@ -678,11 +737,16 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
 
     int NT = (Nk + 63) / 64;
     if constexpr (CAUSAL) NT = min(NT, (min(qb * 128 + 127, N - 1) + p.off) / 64 + 1);
+    int tbeg = 0;   // local: key tiles [tbeg, NT), never empty (the key i + off of the first query lies in both)
+    if constexpr (LOCAL) {
+        tbeg = max(0, qb * 128 + p.off - p.left) / 64;
+        NT = min(NT, (min(qb * 128 + 127, N - 1) + p.off + p.right) / 64 + 1);
+    }
     char* const st0 = smem;
     char* const st1 = smem + STAGE;
-    fill(st0, 0);
+    fill(st0, tbeg);
     __syncthreads();
-    for (int t = 0; t < NT; t += 2) {
+    for (int t = tbeg; t < NT; t += 2) {
         fill(st1, min(t + 1, NT - 1));
         compute(st0, t);
         __syncthreads();
@@ -706,7 +770,14 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
 // sees the block's first key, a wave skips the tiles before its own first key, and S is
 // selected to -inf after the MFMA chain (the accumulators start from the row constants) on
 // the tiles that straddle the wave's diagonal.
-template <class T, int D, int DV, bool CAUSAL = false>
+//
+// LOCAL: key j is seen by the queries j - off - right <= i <= j - off + left, so the block's
+// query tiles are [t0, t1) of that range over its 128 keys.  The range is EMPTY for a block
+// whose keys lie left of every window (Nk > N + left: a KV cache longer than the window): the
+// whole pipeline (row constants, DMA, barriers) is then skipped, block-uniformly, and the
+// zero accumulators are stored.  A wave skips the tiles outside its own keys' range and
+// selects on the tiles that straddle either diagonal.
+template <class T, int D, int DV, bool CAUSAL = false, bool LOCAL = false>
 __global__ __launch_bounds__(256, 2) void bwd_dkdv_fast(BwdParams p) {
     typedef typename Frag8<T>::type F8;
     constexpr int QB = D * 128, OB = DV * 128, STAGE = QB + OB + 512;
@@ -762,10 +833,13 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_fast(BwdParams p) {
         dma_image<DV>(ors, st + QB, N, t * 64, wave, lane);
     };
     int wk0 = 0;   // causal: the wave's first key minus off (the first query that sees it), a scalar
-    if constexpr (CAUSAL) wk0 = kblk * 128 + __builtin_amdgcn_readfirstlane(wave) * 32 - p.off;
+    if constexpr (CAUSAL || LOCAL) wk0 = kblk * 128 + __builtin_amdgcn_readfirstlane(wave) * 32 - p.off;
     auto compute = [&](const char* st, int t) {
         if constexpr (CAUSAL) {
             if (t * 64 + 63 < wk0) return;   // wave-uniform: no query of the tile sees the wave's keys
+        }
+        if constexpr (LOCAL) {
+            if (t * 64 + 63 < wk0 - p.right || t * 64 > wk0 + 31 + p.left) return;
         }
         const char* qimg = st;
         const char* oimg = st + QB;
@@ -799,6 +873,25 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_fast(BwdParams p) {
                         if ((x & 7) + 16 * (x >> 3) < lk) sa[x] = kNegInf;
                 }
             }
+            if constexpr (LOCAL) {
+                // query row q0 + ql (relative to the wave's first key minus off) sees key r iff
+                // q0 + ql - left <= r <= q0 + ql + right; lane terms rebuilt from the lane id as above
+                const int q0 = t * 64 + u * 32 - wk0;
+                if (q0 + p.right < 31) {            // the block's first row misses the wave's last key on the right
+                    const int ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+                    const int lk = (ln & 31) - 8 * (ln >> 5) - q0 - p.right;
+#pragma unroll
+                    for (int x = 0; x < 16; ++x)
+                        if ((x & 7) + 16 * (x >> 3) < lk) sa[x] = kNegInf;
+                }
+                if (q0 + 31 > p.left) {             // its last row misses the wave's first key on the left
+                    const int ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+                    const int lk = (ln & 31) - 8 * (ln >> 5) - q0 + p.left;
+#pragma unroll
+                    for (int x = 0; x < 16; ++x)
+                        if ((x & 7) + 16 * (x >> 3) > lk) sa[x] = kNegInf;
+                }
+            }
             F8 pf[2], dsf[2];
 #pragma unroll
             for (int x = 0; x < 16; ++x) {
@@ -822,22 +915,30 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_fast(BwdParams p) {
     char* const st1 = smem + STAGE;
     int t0 = 0;   // causal: the first query tile that sees the block's first key (< NT: see DESIGN §2.7)
     if constexpr (CAUSAL) t0 = min(max(0, kblk * 128 - p.off) / 64, NT - 1);
-    load_rowc(t0);
-    fill(st0, t0);
-    store_rowc(st0);
-    __syncthreads();
-    for (int t = t0; t < NT; t += 2) {
-        load_rowc(min(t + 1, NT - 1));
-        fill(st1, min(t + 1, NT - 1));
-        compute(st0, t);
-        store_rowc(st1);
+    int t1 = NT;   // local: query tiles [t0, t1), possibly none
+    if constexpr (LOCAL) {
+        const int qhi = kblk * 128 + 127 - p.off + p.left;   // the last query that sees the block's last key
+        t0 = max(0, kblk * 128 - p.off - p.right) / 64;
+        t1 = qhi < 0 ? 0 : min(NT, qhi / 64 + 1);
+    }
+    if (!LOCAL || t0 < t1) {   // (block-uniform: no prefetch of a tile that does not exist, no uneven barrier)
+        load_rowc(t0);
+        fill(st0, t0);
+        store_rowc(st0);
         __syncthreads();
-        if (t + 1 < NT) {
-            load_rowc(min(t + 2, NT - 1));
-            fill(st0, min(t + 2, NT - 1));
-            compute(st1, t + 1);
-            store_rowc(st0);
+        for (int t = t0; t < t1; t += 2) {
+            load_rowc(min(t + 1, t1 - 1));
+            fill(st1, min(t + 1, t1 - 1));
+            compute(st0, t);
+            store_rowc(st1);
             __syncthreads();
+            if (t + 1 < t1) {
+                load_rowc(min(t + 2, t1 - 1));
+                fill(st0, min(t + 2, t1 - 1));
+                compute(st1, t + 1);
+                store_rowc(st0);
+                __syncthreads();
+            }
         }
     }
     if (kj < Nk) {
@@ -1673,8 +1774,13 @@ static hipError_t launch_fast_dd(const DenseBwdPlan& pl, BwdParams p, hipStream_
         p.fin = p.flags + ff.fin;
     }
     // (causal: always the two passes: no atomics, no hand-off)
-    pass(p.causal ? bwd_dq_fast<T, D, DV, true> : bwd_dq_fast<T, D, DV>, p.N);
-    if (!single) pass(p.causal ? bwd_dkdv_fast<T, D, DV, true> : bwd_dkdv_fast<T, D, DV>, p.Nk);
+    // (local: likewise)
+    pass(p.local ? bwd_dq_fast<T, D, DV, false, true> : p.causal ? bwd_dq_fast<T, D, DV, true> : bwd_dq_fast<T, D, DV>, p.N);
+    if (!single)
+        pass(p.local    ? bwd_dkdv_fast<T, D, DV, false, true>
+             : p.causal ? bwd_dkdv_fast<T, D, DV, true>
+                        : bwd_dkdv_fast<T, D, DV>,
+             p.Nk);
     return hipGetLastError();
 }
 template <class T>
@@ -1693,8 +1799,10 @@ static hipError_t launch_generic(const BwdParams& p, hipStream_t s) {
     const size_t rows = kGT * (2 * (p.d + 1) + 2 * (p.dv + 1));
     const size_t sm_dq = sizeof(A) * (rows + kGT * (kGT + 1));
     const size_t sm_kv = sizeof(A) * (rows + 2 * kGT * (kGT + 1));
-    void (*dq)(BwdParams) = p.causal ? bwd_generic_dq<T, A, true> : bwd_generic_dq<T, A>;
-    void (*dkdv)(BwdParams) = p.causal ? bwd_generic_dkdv<T, A, true> : bwd_generic_dkdv<T, A>;
+    void (*dq)(BwdParams) = p.local ? bwd_generic_dq<T, A, false, true> : p.causal ? bwd_generic_dq<T, A, true> : bwd_generic_dq<T, A>;
+    void (*dkdv)(BwdParams) = p.local    ? bwd_generic_dkdv<T, A, false, true>
+                              : p.causal ? bwd_generic_dkdv<T, A, true>
+                                         : bwd_generic_dkdv<T, A>;
     // > 64 KiB of dynamic LDS at d = dv = 128 (gfx950 has 160 KiB per CU)
     (void)hipFuncSetAttribute((const void*)dq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_dq);
     (void)hipFuncSetAttribute((const void*)dkdv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_kv);
@@ -1728,11 +1836,15 @@ static DenseBwdKnobs bwd_knobs() { return {g_bwd_force_generic, g_bwd_mode, g_bw
 // The shape's own needs under the thread's knobs on the current device: aligned tensors, room
 // for everything (the queries have no pointers).
 size_t dense_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    return dense_bwd_plan(dtype, N, Nk, d, dv, batch, false, bwd_knobs(), true, SIZE_MAX, device_cus(nullptr)).total;
+    return dense_bwd_plan(dtype, N, Nk, d, dv, batch, kMaskNone, bwd_knobs(), true, SIZE_MAX, device_cus(nullptr)).total;
 }
 // fa_causal_bwd: header, row statistics, padded slabs; never the single pass's part (and so no device query)
 size_t causal_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    return dense_bwd_plan(dtype, N, Nk, d, dv, batch, true, bwd_knobs(), true, SIZE_MAX, 0).total;
+    return dense_bwd_plan(dtype, N, Nk, d, dv, batch, kMaskCausal, bwd_knobs(), true, SIZE_MAX, 0).total;
+}
+// fa_local_bwd: the same, whatever the window
+size_t local_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
+    return dense_bwd_plan(dtype, N, Nk, d, dv, batch, kMaskLocal, bwd_knobs(), true, SIZE_MAX, 0).total;
 }
 
 // Single-pass state in the workspace: per-slice counters (zeroed here), then the running dQ
@@ -1792,6 +1904,10 @@ int launch_dense_bwd(const DenseBwdArgs& a, hipStream_t s, const char** why) {
         *why = "causal attention needs Nk >= N (a query would see no key)";
         return FA_ERR_UNSUPPORTED;
     }
+    if (a.local && a.Nk < a.N) {
+        *why = "local attention needs Nk >= N (a query would see no key)";
+        return FA_ERR_UNSUPPORTED;
+    }
     if (a.N * a.d > INT32_MAX || a.Nk * a.d > INT32_MAX || a.N * a.dv > INT32_MAX ||
         a.Nk * a.dv > INT32_MAX || a.N * a.batch > INT32_MAX / 2 || a.Nk * a.batch > INT32_MAX / 2) {
         *why = "extent exceeds 2^31 elements";
@@ -1800,18 +1916,25 @@ int launch_dense_bwd(const DenseBwdArgs& a, hipStream_t s, const char** why) {
     const DenseBwdKnobs kn = bwd_knobs();
     char* const w = al256(a.workspace);
     const size_t slack = (size_t)(w - (char*)a.workspace);
-    const DenseBwdPlan pl = dense_bwd_plan(a.dtype, a.N, a.Nk, a.d, a.dv, a.batch, a.causal != 0, kn,
+    const DenseBwdPlan pl = dense_bwd_plan(a.dtype, a.N, a.Nk, a.d, a.dv, a.batch, dense_mask(a.causal, a.local), kn,
                                            aligned16(a.Q) && aligned16(a.K) && aligned16(a.V) && aligned16(a.dO),
                                            a.workspace_bytes > slack ? a.workspace_bytes - slack : 0, device_cus(s));
-    // causal and Float64 totals depend on the shape alone: the whole of it must be there.
+    // causal, local and Float64 totals depend on the shape alone: the whole of it must be there.
     // (A padded call checks its slabs below; the single pass's part is optional.)
-    if ((a.causal || a.dtype == FA_DTYPE_F64) && a.workspace_bytes < pl.total) {
-        *why = a.causal ? "workspace smaller than fa_causal_bwd_workspace()" : "workspace smaller than fa_dense_bwd_workspace()";
+    if ((a.causal || a.local || a.dtype == FA_DTYPE_F64) && a.workspace_bytes < pl.total) {
+        *why = a.local    ? "workspace smaller than fa_local_bwd_workspace()"
+               : a.causal ? "workspace smaller than fa_causal_bwd_workspace()"
+                          : "workspace smaller than fa_dense_bwd_workspace()";
         return FA_ERR_WORKSPACE;
     }
     BwdParams p;
-    p.causal = a.causal ? 1 : 0;
-    p.off = a.causal ? (int)(a.Nk - a.N) : 0;   // from the caller's extents, also on the padded path
+    p.causal = a.causal && !a.local ? 1 : 0;
+    p.off = a.causal || a.local ? (int)(a.Nk - a.N) : 0;   // from the caller's extents, also on the padded path
+    if (a.local) {   // the window too
+        p.local = 1;
+        p.left = local_clamp(a.left, a.Nk);
+        p.right = local_clamp(a.right, a.Nk);
+    }
     p.Q = a.Q; p.K = a.K; p.V = a.V; p.O = a.O; p.dO = a.dO; p.l = a.l; p.m = a.m;
     p.dQ = a.dQ; p.dK = a.dK; p.dV = a.dV;
     p.hdr = (unsigned*)(w + pl.off_hdr);

@@ -1,4 +1,4 @@
-// fa_dense_plan.h — the HOST PLANS of the dense (and causal) attention forward
+// fa_dense_plan.h — the HOST PLANS of the dense (and causal, and local) attention forward
 // (fa_fwd.hip, fa_fwd_p4.hip) and backward (fa_bwd.hip): which kernel a call gets, on what
 // grid, and where every region of its workspace lies.  dense_fwd_plan and dense_bwd_plan
 // are pure functions of the shape, a snapshot of the debug knobs, the pointer-alignment
@@ -33,7 +33,8 @@ enum DenseFwdVariant : int {
 };
 
 // The causal twins (causal_fwd_*, the CAUSAL instantiations of the generic kernels) are the
-// same enumerator with DenseFwdPlan::causal != 0.
+// same enumerator with DenseFwdPlan::causal != 0, the local ones (local_fwd_*, the LOCAL
+// instantiations) with DenseFwdPlan::local.
 enum DenseFwdKernel : int {
     kDenseFwdNone = -1,        // a head dimension above kMaxHeadDim: the launcher refuses
     kDenseFwdGeneric = 0,      // dense_fwd_generic (SIMT, any shape and alignment)
@@ -58,6 +59,7 @@ struct DenseFwdPlan {
     // FwdParams::causal: 0 dense; bit 0 causal, bit 1 a slab's heaviest query block first,
     // bit 2 block-major inside an XCD's share of the grid (dense_fwd_tiled)
     int causal = 0;
+    bool local = false;    // fa_local_fwd: the LOCAL instantiations (never with causal bits, never split, never p4)
     bool kv_vec = false;   // FwdParams::fast: K / V rows take 16-B loads (after padding, if any)
     bool wide = false;     // FwdParams::wide: N % 8 == 0, Q and O 16-B aligned
     bool pad = false;      // K / V are first copied to zero-padded slabs of row stride ldk
@@ -112,9 +114,11 @@ inline DenseFwdSplit dense_fwd_split(int dtype, int64_t N, int64_t Nk, int64_t d
 // ragged last tile.  The workspace query reserves the slabs only when the SHAPE needs them
 // (it has no pointers); without room for them those calls run the generic kernel.
 inline DenseFwdPlan dense_fwd_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch,
-                                   bool causal, DenseFwdKnobs kn, bool kv_aligned16, bool qo_aligned16,
+                                   DenseMask mask, DenseFwdKnobs kn, bool kv_aligned16, bool qo_aligned16,
                                    size_t ws_bytes, int cus) {
     DenseFwdPlan pl;
+    const bool causal = mask == kMaskCausal;
+    pl.local = mask == kMaskLocal;
     if (dtype == FA_DTYPE_F64) {
         pl.kernel = kDenseFwdF64;
         return pl;
@@ -126,7 +130,7 @@ inline DenseFwdPlan dense_fwd_plan(int dtype, int64_t N, int64_t Nk, int64_t d, 
                           nk8 * (d > dv ? d : dv) * batch < ((int64_t)1 << 40);
     const size_t kbytes = al256((size_t)(nk8 * d * batch) * 2), vbytes = al256((size_t)(nk8 * dv * batch) * 2);
     const size_t pad_bytes = kbytes + vbytes + 256;
-    const DenseFwdSplit shape_split = causal ? DenseFwdSplit{} : dense_fwd_split(dtype, N, Nk, d, dv, batch);
+    const DenseFwdSplit shape_split = mask != kMaskNone ? DenseFwdSplit{} : dense_fwd_split(dtype, N, Nk, d, dv, batch);
     const size_t obytes = al256((size_t)(shape_split.nsplit * batch * N * dv) * 4);
     const size_t lmbytes = al256((size_t)(shape_split.nsplit * batch * N) * 4);
     const size_t split_bytes = obytes + 2 * lmbytes + 256;
@@ -175,12 +179,13 @@ inline DenseFwdPlan dense_fwd_plan(int dtype, int64_t N, int64_t Nk, int64_t d, 
     // <= 64: 8 waves x 2 query blocks (512 rows / workgroup); 128: 8 waves x 1
     const bool q2_class = Dc <= 64 && DVc <= 64;
     pl.block = 512;
-    if (causal) {   // the class's default geometry: no variant, no split, no p4
+    if (mask != kMaskNone) {   // the class's default geometry: no variant, no split, no p4
         pl.rows = q2_class ? 512 : 256;
         pl.nqb = ceil_div(N, pl.rows);
         pl.grid = pl.total_wg = pl.nqb * batch;
         // order 2 needs every XCD's share of the grid to hold whole slabs
-        if (kn.causal_order == 2 && pl.total_wg % 8 == 0 && (pl.total_wg / 8) % pl.nqb == 0) pl.causal = 1 | 4;
+        // (local launches keep the default order: a bounded band makes the blocks near-uniform)
+        if (causal && kn.causal_order == 2 && pl.total_wg % 8 == 0 && (pl.total_wg / 8) % pl.nqb == 0) pl.causal = 1 | 4;
         pl.kernel = q2_class ? (pl.wide ? kDenseFwdW8Q2Wide : kDenseFwdW8Q2) : (pl.wide ? kDenseFwdW8B64Wide : kDenseFwdW8B64);
         return pl;
     }
@@ -334,10 +339,10 @@ inline bool bwd_shape_fast(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t 
 // slab when K <= CUs/8 and the slab count is a multiple of 8 (a slab's members then run
 // together: speed, not correctness, which needs no co-residency); in kBwdAuto only when the
 // grid fills the chip and K divides the CUs a slab's members are dealt over (one XCD's, or
-// the chip's), so no slab waits part-resident behind another.  Never for causal launches
-// (no atomics, no hand-off there).  A workspace too small for its part gets the two passes.
+// the chip's), so no slab waits part-resident behind another.  Never for causal or local
+// launches (no atomics, no hand-off there).  A workspace too small for its part gets the two passes.
 inline DenseBwdPlan dense_bwd_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch,
-                                   bool causal, DenseBwdKnobs kn, bool qkvdo_aligned16, size_t ws_bytes, int cus) {
+                                   DenseMask mask, DenseBwdKnobs kn, bool qkvdo_aligned16, size_t ws_bytes, int cus) {
     DenseBwdPlan pl;
     pl.N = N; pl.Nk = Nk; pl.d = d; pl.dv = dv;
     pl.off_hdr = 0;
@@ -389,7 +394,7 @@ inline DenseBwdPlan dense_bwd_plan(int dtype, int64_t N, int64_t Nk, int64_t d, 
     if (!fast && !pl.padded) return pl;   // kDenseBwdGeneric
     pl.kernel = kDenseBwdTwoPass;
     const int64_t K = ceil_div(pl.Nk, 256), T = ceil_div(pl.N, 64);
-    if (causal || kn.mode == kBwdTwoPass || cus < 8 || kn.hoff * K > T || K > cus || batch * K > INT32_MAX / 2 ||
+    if (mask != kMaskNone || kn.mode == kBwdTwoPass || cus < 8 || kn.hoff * K > T || K > cus || batch * K > INT32_MAX / 2 ||
         2 * T * (pl.d / 16) * 4096 >= INT32_MAX || T >= (1 << 20))   // a slice index fits the 20 bits bwd_fused packs it in
         return pl;
     const int xcd = (K <= cus / 8 && batch % 8 == 0 && kn.xcd != 0) ? 1 : 0;

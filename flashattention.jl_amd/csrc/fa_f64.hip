@@ -38,6 +38,8 @@ struct F64Params {
     int N, Nk, d, dv, nqb;
     double scale;
     int causal = 0, off = 0;   // CAUSAL instantiations: query i sees keys j <= i + off (off = Nk - N)
+    // LOCAL instantiations: keys i + off - left <= j <= i + off + right, each side in [0, Nk] (local_clamp)
+    int local = 0, left = 0, right = 0;
 };
 
 constexpr int kQB64 = 64;    // queries per workgroup (QB = 16 for grids smaller than the chip)
@@ -53,7 +55,7 @@ static size_t f64_lds_bytes(int d, int dv, bool stats, int QB) {
 
 // QB queries per workgroup, NG = 256/QB thread groups per query: group g scores
 // keys KPG·g .. KPG·g + KPG−1 of each tile and owns output channels g, g + NG, ….
-template <bool STATS, int QB, bool CAUSAL = false>
+template <bool STATS, int QB, bool CAUSAL = false, bool LOCAL = false>
 __global__ __launch_bounds__(kTh64) void dense_fwd_f64(F64Params p) {
     constexpr int NG = kTh64 / QB, KPG = kKB64 / NG, OPER = kMaxHeadDim / NG;
     static_assert(KPG >= 1 && QB * NG == kTh64, "geometry");
@@ -83,7 +85,15 @@ __global__ __launch_bounds__(kTh64) void dense_fwd_f64(F64Params p) {
     // query, so m_run is finite after the first tile and a masked score gives exp(-inf) = 0
     int kend = Nk;
     if constexpr (CAUSAL) kend = min(Nk, min(q0 + QB - 1, N - 1) + p.off + 1);
-    for (int k0 = 0; k0 < kend; k0 += kKB64) {
+    // local: from the workgroup's first query's left edge to its last real query's right edge.  A
+    // query whose window begins in a later tile has m_run = -inf after a tile: its alpha is 1
+    // and its P are 0 there (not the NaN of -inf - -inf)
+    int kbeg = 0;
+    if constexpr (LOCAL) {
+        kbeg = max(0, q0 + p.off - p.left) / kKB64 * kKB64;
+        kend = min(Nk, min(q0 + QB - 1, N - 1) + p.off + p.right + 1);
+    }
+    for (int k0 = kbeg; k0 < kend; k0 += kKB64) {
         __syncthreads();   // the previous tile's K / V / P readers are done
         for (int i = tid; i < kKB64 * d; i += kTh64) {
             const int f = i >> 5, k = i & 31;
@@ -111,6 +121,8 @@ __global__ __launch_bounds__(kTh64) void dense_fwd_f64(F64Params p) {
         for (int j = 0; j < KPG; ++j) {
             bool vis = k0 + KPG * g + j < Nk;
             if constexpr (CAUSAL) vis = vis && k0 + KPG * g + j <= q0 + qi + p.off;
+            if constexpr (LOCAL)
+                vis = vis && k0 + KPG * g + j <= q0 + qi + p.off + p.right && k0 + KPG * g + j >= q0 + qi + p.off - p.left;
             s[j] = vis ? s[j] * p.scale : -__builtin_huge_val();
             mx = dmax(mx, s[j]);
         }
@@ -121,11 +133,13 @@ __global__ __launch_bounds__(kTh64) void dense_fwd_f64(F64Params p) {
 #pragma unroll
         for (int gg = 1; gg < NG; ++gg) tmax = dmax(tmax, red[gg * QB + qi]);
         const double m_new = dmax(m_run, tmax);
-        const double alpha = exp(m_run - m_new);
+        double alpha = exp(m_run - m_new);
+        const bool none = LOCAL && m_new == -__builtin_huge_val();   // no visible key so far
+        if (none) alpha = 1.0;
         double ps = 0.0;
 #pragma unroll
         for (int j = 0; j < KPG; ++j) {
-            const double pj = exp(s[j] - m_new);
+            const double pj = none ? 0.0 : exp(s[j] - m_new);
             ps += pj;
             if (!STATS) sP[qi * (kKB64 + 1) + KPG * g + j] = pj;
         }
@@ -186,13 +200,18 @@ __global__ __launch_bounds__(256) void bwd_rowdot_f64(const double* __restrict__
     nD[idx] = -acc;
 }
 
-static bool f64_fits(int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, const char** why, int causal = 0) {
+static bool f64_fits(int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, const char** why, int causal = 0,
+                     int local = 0) {
     if (d > kMaxHeadDim || dv > kMaxHeadDim) {
         *why = "head dimension exceeds the compiled maximum (128)";
         return false;
     }
     if (causal && Nk < N) {
         *why = "causal attention needs Nk >= N (a query would see no key)";
+        return false;
+    }
+    if (local && Nk < N) {
+        *why = "local attention needs Nk >= N (a query would see no key)";
         return false;
     }
     if (N > INT32_MAX / 2 || Nk > INT32_MAX / 2 || (N + kQB64 - 1) / kQB64 * batch > INT32_MAX) {
@@ -206,6 +225,12 @@ template <bool STATS, int QB>
 static hipError_t launch_f64_qb(F64Params p, int64_t batch, hipStream_t s) {
     p.nqb = (p.N + QB - 1) / QB;
     const size_t lds = f64_lds_bytes(p.d, p.dv, STATS, QB);
+    if (p.local) {
+        (void)hipFuncSetAttribute((const void*)dense_fwd_f64<STATS, QB, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds);
+        hipLaunchKernelGGL((dense_fwd_f64<STATS, QB, false, true>), dim3((unsigned)(p.nqb * batch)), dim3(kTh64), lds, s, p);
+        return hipGetLastError();
+    }
     if (p.causal) {
         (void)hipFuncSetAttribute((const void*)dense_fwd_f64<STATS, QB, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)lds);
@@ -226,15 +251,20 @@ static hipError_t launch_f64_kernel(const F64Params& p, int64_t batch, hipStream
 }
 
 int launch_dense_fwd_f64(const DenseArgs& a, hipStream_t s, const char** why) {
-    if (!f64_fits(a.N, a.Nk, a.d, a.dv, a.batch, why, a.causal)) return FA_ERR_UNSUPPORTED;
+    if (!f64_fits(a.N, a.Nk, a.d, a.dv, a.batch, why, a.causal, a.local)) return FA_ERR_UNSUPPORTED;
     F64Params p;
     p.Q = (const double*)a.Q; p.K = (const double*)a.K; p.V = (const double*)a.V; p.O = (double*)a.O;
     p.l = a.l; p.m = a.m; p.nlse = nullptr;
     p.N = (int)a.N; p.Nk = (int)a.Nk; p.d = (int)a.d; p.dv = (int)a.dv;
     p.nqb = (int)((a.N + kQB64 - 1) / kQB64);
     p.scale = a.scale64 > 0.0 ? a.scale64 : (double)a.scale;
-    p.causal = a.causal ? 1 : 0;
-    p.off = a.causal ? (int)(a.Nk - a.N) : 0;
+    p.causal = a.causal && !a.local ? 1 : 0;
+    p.off = a.causal || a.local ? (int)(a.Nk - a.N) : 0;
+    if (a.local) {
+        p.local = 1;
+        p.left = local_clamp(a.left, a.Nk);
+        p.right = local_clamp(a.right, a.Nk);
+    }
     const hipError_t e = launch_f64_kernel<false>(p, a.batch, s);
     if (e != hipSuccess) {
         *why = hipGetErrorString(e);
@@ -244,15 +274,20 @@ int launch_dense_fwd_f64(const DenseArgs& a, hipStream_t s, const char** why) {
 }
 
 int launch_f64_bwd_stats(const DenseBwdArgs& a, double* nD, double* nlse, hipStream_t s, const char** why) {
-    if (!f64_fits(a.N, a.Nk, a.d, a.dv, a.batch, why, a.causal)) return FA_ERR_UNSUPPORTED;
+    if (!f64_fits(a.N, a.Nk, a.d, a.dv, a.batch, why, a.causal, a.local)) return FA_ERR_UNSUPPORTED;
     F64Params p;
     p.Q = (const double*)a.Q; p.K = (const double*)a.K; p.V = nullptr; p.O = nullptr;
     p.l = nullptr; p.m = nullptr; p.nlse = nlse;
     p.N = (int)a.N; p.Nk = (int)a.Nk; p.d = (int)a.d; p.dv = (int)a.dv;
     p.nqb = (int)((a.N + kQB64 - 1) / kQB64);
     p.scale = a.scale64 > 0.0 ? a.scale64 : (double)a.scale;
-    p.causal = a.causal ? 1 : 0;
-    p.off = a.causal ? (int)(a.Nk - a.N) : 0;
+    p.causal = a.causal && !a.local ? 1 : 0;
+    p.off = a.causal || a.local ? (int)(a.Nk - a.N) : 0;
+    if (a.local) {
+        p.local = 1;
+        p.left = local_clamp(a.left, a.Nk);
+        p.right = local_clamp(a.right, a.Nk);
+    }
     hipError_t e = launch_f64_kernel<true>(p, a.batch, s);
     if (e == hipSuccess) {
         const int64_t total = a.N * a.batch;

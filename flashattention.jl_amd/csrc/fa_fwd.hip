@@ -124,10 +124,26 @@ __device__ __forceinline__ int causal_ntiles(int nt, int q_last, int N, int off,
     return min(nt, (min(q_last, N - 1) + off) / bn + 1);
 }
 
+// Local launches (fa_local_fwd; LOCAL instantiations, never CAUSAL and never SPLIT): query i sees
+// keys i + off - wleft <= j <= i + off + wright, off = Nk - N >= 0.  The host clamps both
+// sides to [0, Nk], and a side equal to Nk binds nowhere (i + off - Nk < 0, i + off + Nk >= Nk),
+// so "no bound" needs no case of its own.  The key i + off exists, so every query sees a
+// key; but with a left edge the first tile a wave computes can hide whole rows (their
+// windows begin in the next tile), so a row's running max can still be -inf after a tile:
+// the LOCAL bodies keep alpha = 1 and exponent offset 0 for such a row (P = exp2(-inf) = 0)
+// instead of the NaN of -inf - -inf.  Tiles of `bn` keys [local_tile0, local_ntiles) of a
+// workgroup with query rows q_first .. q_last.
+__device__ __forceinline__ int local_tile0(int q_first, int off, int wleft, int bn) {
+    return max(0, q_first + off - wleft) / bn;
+}
+__device__ __forceinline__ int local_ntiles(int nt, int q_last, int N, int off, int wright, int bn) {
+    return min(nt, (min(q_last, N - 1) + off + wright) / bn + 1);
+}
+
 // --------------------------------------------------------------------------
 // bf16 / fp16 forward (v_mfma_f32_32x32x16_{bf16,f16})
 // --------------------------------------------------------------------------
-template <class T, int D, int DV, bool CAUSAL = false>
+template <class T, int D, int DV, bool CAUSAL = false, bool LOCAL = false>
 __global__ __launch_bounds__(kThreads) void dense_fwd_generic(FwdParams p) {
     typedef typename Frag8<T>::type F8;
     typedef typename Frag8<T>::half F4;
@@ -214,11 +230,16 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic(FwdParams p) {
     int ntiles = (Nk + kBN - 1) / kBN;
     if constexpr (CAUSAL)   // tiles up to the block's last query's last visible key (causal_ntiles)
         ntiles = causal_ntiles(ntiles, qb * kBM + kBM - 1, N, (Nk - N), kBN);
-    gload(0);
+    int jbeg = 0;
+    if constexpr (LOCAL) {   // the tiles between the block's first query's left edge and its last query's right edge
+        jbeg = local_tile0(qb * kBM, Nk - N, p.wleft, kBN);
+        ntiles = local_ntiles(ntiles, qb * kBM + kBM - 1, N, Nk - N, p.wright, kBN);
+    }
+    gload(jbeg);
     lstore();
     __syncthreads();
 
-    for (int j = 0; j < ntiles; ++j) {
+    for (int j = jbeg; j < ntiles; ++j) {
         const bool more = j + 1 < ntiles;
         if (more) gload(j + 1);
 
@@ -260,6 +281,18 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic(FwdParams p) {
                     }
             }
         }
+        if constexpr (LOCAL) {   // after the ragged mask; only on tiles that straddle an edge of the wave's band
+            const int w0 = qb * kBM + wave * 32 + (Nk - N);
+            if (key0 + kBN - 1 > w0 + p.wright || key0 < w0 + 31 - p.wleft) {
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                    for (int x = 0; x < 16; ++x) {
+                        const int kt = key0 + kb * 32 + (x & 3) + 4 * ((x >> 2) & 1) + 8 * h + 16 * (x >> 3);
+                        if (kt > qi + (Nk - N) + p.wright || kt < qi + (Nk - N) - p.wleft) sacc[kb][x] = kNegInf;
+                    }
+            }
+        }
 
         // ---- online softmax (raw dot-product units; exp2 with folded scale) ----
         float mt = kNegInf;
@@ -269,15 +302,23 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic(FwdParams p) {
             for (int x = 0; x < 16; ++x) mt = fmaxf(mt, sacc[kb][x]);
         mt = swap_halves_max(mt);
         const float m_new = fmaxf(m_run, mt);
-        const float alpha = exp2_fast((m_run - m_new) * c);
+        float alpha = exp2_fast((m_run - m_new) * c);
         const float mc = m_new * c;
+        // LOCAL: a row with no visible key so far keeps alpha = 1 and subtracts 0 (no -inf - -inf,
+        // local_tile0's comment); the exponent is (s - m) c, exactly 0 for the row's max, so that
+        // a query with one visible key gets l = 1 and that key's V bit for bit (dense_fwd_tiled)
+        float msub = 0.0f;
+        if constexpr (LOCAL) {
+            msub = m_new == kNegInf ? 0.0f : m_new;
+            if (m_new == kNegInf) alpha = 1.0f;
+        }
         float ls = 0.0f;
         F8 pf[2][2];
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
             for (int x = 0; x < 16; ++x) {
-                const float pv = exp2_fast(fmaf(sacc[kb][x], c, -mc));
+                const float pv = exp2_fast(LOCAL ? (sacc[kb][x] - msub) * c : fmaf(sacc[kb][x], c, -mc));
                 ls += pv;
                 pf[kb][x >> 3][x & 7] = (T)pv;
             }
@@ -328,7 +369,7 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic(FwdParams p) {
 // --------------------------------------------------------------------------
 // fp32 forward (exact f32 MFMA v_mfma_f32_32x32x2_f32)
 // --------------------------------------------------------------------------
-template <int D, int DV, bool CAUSAL = false>
+template <int D, int DV, bool CAUSAL = false, bool LOCAL = false>
 __global__ __launch_bounds__(kThreads) void dense_fwd_generic_f32(FwdParams p) {
     constexpr int KROWF = kBN;       // K image [D][64] floats
     constexpr int VROWF = kBN + 1;   // V image [DV][65] floats (pad → conflict-free column reads)
@@ -398,11 +439,16 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic_f32(FwdParams p) {
     int ntiles = (Nk + kBN - 1) / kBN;
     if constexpr (CAUSAL)   // tiles up to the block's last query's last visible key (causal_ntiles)
         ntiles = causal_ntiles(ntiles, qb * kBM + kBM - 1, N, (Nk - N), kBN);
-    gload(0);
+    int jbeg = 0;
+    if constexpr (LOCAL) {   // the tiles between the block's first query's left edge and its last query's right edge
+        jbeg = local_tile0(qb * kBM, Nk - N, p.wleft, kBN);
+        ntiles = local_ntiles(ntiles, qb * kBM + kBM - 1, N, Nk - N, p.wright, kBN);
+    }
+    gload(jbeg);
     lstore();
     __syncthreads();
 
-    for (int j = 0; j < ntiles; ++j) {
+    for (int j = jbeg; j < ntiles; ++j) {
         const bool more = j + 1 < ntiles;
         if (more) gload(j + 1);
 
@@ -433,6 +479,18 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic_f32(FwdParams p) {
                         if (key0 + kb * 32 + acc_row(x, h) > qi + (Nk - N)) sacc[kb][x] = kNegInf;
             }
         }
+        if constexpr (LOCAL) {
+            const int w0 = qb * kBM + wave * 32 + (Nk - N);
+            if (key0 + kBN - 1 > w0 + p.wright || key0 < w0 + 31 - p.wleft) {
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                    for (int x = 0; x < 16; ++x) {
+                        const int kt = key0 + kb * 32 + acc_row(x, h);
+                        if (kt > qi + (Nk - N) + p.wright || kt < qi + (Nk - N) - p.wleft) sacc[kb][x] = kNegInf;
+                    }
+            }
+        }
 
         float mt = kNegInf;
 #pragma unroll
@@ -441,14 +499,22 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic_f32(FwdParams p) {
             for (int x = 0; x < 16; ++x) mt = fmaxf(mt, sacc[kb][x]);
         mt = swap_halves_max(mt);
         const float m_new = fmaxf(m_run, mt);
-        const float alpha = exp2_fast((m_run - m_new) * c);
+        float alpha = exp2_fast((m_run - m_new) * c);
         const float mc = m_new * c;
+        // LOCAL: a row with no visible key so far keeps alpha = 1 and subtracts 0 (no -inf - -inf,
+        // local_tile0's comment); the exponent is (s - m) c, exactly 0 for the row's max, so that
+        // a query with one visible key gets l = 1 and that key's V bit for bit (dense_fwd_tiled)
+        float msub = 0.0f;
+        if constexpr (LOCAL) {
+            msub = m_new == kNegInf ? 0.0f : m_new;
+            if (m_new == kNegInf) alpha = 1.0f;
+        }
         float ls = 0.0f;
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
             for (int x = 0; x < 16; ++x) {
-                const float pv = exp2_fast(fmaf(sacc[kb][x], c, -mc));
+                const float pv = exp2_fast(LOCAL ? (sacc[kb][x] - msub) * c : fmaf(sacc[kb][x], c, -mc));
                 ls += pv;
                 sacc[kb][x] = pv;
             }
@@ -523,9 +589,20 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic_f32(FwdParams p) {
 // last visible key; loads, LDS stores and the barrier stay workgroup-uniform; a wave whose
 // last query is before a tile's first key skips that tile's compute, and the per-element
 // select runs only on tiles that straddle the wave's diagonal (both tests wave-uniform).
-template <class T, int D, int DV, int NW, int BN, int NQB, bool SPLIT = false, bool WIDE = false, bool CAUSAL = false>
+//
+// LOCAL (fa_local_fwd; never with SPLIT or CAUSAL; the window is in p.wleft / p.wright, see
+// local_tile0): the workgroup's tiles run from its first query's left edge to its last query's
+// right edge, in the default launch order (a bounded band makes the blocks near-uniform); a
+// wave computes a tile only if some query of it sees the tile, and selects on the tiles that
+// straddle its left or its right diagonal (all tests wave-uniform; both edges and the
+// ragged mask can meet in one tile).  A row whose window begins after the wave's first tile
+// keeps m_used = -inf there: the rescale is row-local as for CAUSAL, with alpha = 1 for a row
+// that does not move, and the exponent's offset is 0 while m_used = -inf (P = 0).
+template <class T, int D, int DV, int NW, int BN, int NQB, bool SPLIT = false, bool WIDE = false, bool CAUSAL = false,
+          bool LOCAL = false>
 __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
     static_assert(!(CAUSAL && SPLIT), "causal launches never split the keys");
+    static_assert(!(LOCAL && (SPLIT || CAUSAL)), "local launches never split the keys; LOCAL is a mode of its own");
     typedef typename Frag8<T>::type F8;
     typedef typename Frag8<T>::half F4;
     constexpr int NTH = 64 * NW;
@@ -606,9 +683,11 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
     const bool ragged = (Nk % BN) != 0;
     // key tiles [jt0, jt1) of this workgroup (all tiles unless split-KV)
     // (causal: up to the last tile any of the workgroup's queries sees)
-    const int jt0 = SPLIT ? split * p.tps : 0;
+    // (local: from the first query's left edge to the last query's right edge; jt0 < jt1)
+    const int jt0 = SPLIT ? split * p.tps : LOCAL ? local_tile0(qb * BM, Nk - N, p.wleft, BN) : 0;
     int jt1 = SPLIT ? min(NT, jt0 + p.tps) : NT;
     if constexpr (CAUSAL) jt1 = causal_ntiles(NT, qb * BM + BM - 1, N, (Nk - N), BN);
+    if constexpr (LOCAL) jt1 = local_ntiles(NT, qb * BM + BM - 1, N, Nk - N, p.wright, BN);
 
     u32x4 kreg[KCH], vreg[VCH];
     auto gload = [&](int j) {
@@ -750,6 +829,39 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
                         }
             }
         }
+        if constexpr (LOCAL) {
+            // the same select on each side of the band: wr, wl are the right and left key limits of
+            // the wave's first query relative to the tile (scalars); the lane term is rebuilt from
+            // the lane id inside each branch, so no mask register lives across the loop
+            const int wf = qb * BM + __builtin_amdgcn_readfirstlane(wave) * NQB * 32 + (Nk - N) - j * BN;
+            const int wr = wf + p.wright, wl = wf - p.wleft;
+            if (BN - 1 > wr) {   // a key past the first query's right limit
+                const int ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+                const int lr = (ln & 31) - 8 * (ln >> 5) + wr;
+#pragma unroll
+                for (int u = 0; u < NQB; ++u)
+#pragma unroll
+                    for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+                        for (int x = 0; x < 16; ++x) {
+                            const int ktc = kb * 32 + (x & 3) + 4 * ((x >> 2) & 1) + 16 * (x >> 3) - 32 * u;
+                            if (ktc > lr) sacc[u][kb][x] = kNegInf;
+                        }
+            }
+            if (wl + NQB * 32 - 1 > 0) {   // a key before the last query's left limit
+                const int ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+                const int ll = (ln & 31) - 8 * (ln >> 5) + wl;
+#pragma unroll
+                for (int u = 0; u < NQB; ++u)
+#pragma unroll
+                    for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+                        for (int x = 0; x < 16; ++x) {
+                            const int ktc = kb * 32 + (x & 3) + 4 * ((x >> 2) & 1) + 16 * (x >> 3) - 32 * u;
+                            if (ktc < ll) sacc[u][kb][x] = kNegInf;
+                        }
+            }
+        }
         F8 pf[NQB][NKB][2];
 #pragma unroll
         for (int u = 0; u < NQB; ++u) {
@@ -767,7 +879,12 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
                     // scores alone, not on what a later row of the wave sees
                     if (!(m_new > m_used[u] + thr_raw)) m_new = m_used[u];
                 }
-                const float alpha = exp2_fast((m_used[u] - m_new) * c);
+                float alpha = exp2_fast((m_used[u] - m_new) * c);
+                if constexpr (LOCAL) {
+                    // row-local as above; a row that stays gets alpha = 1 outright, since at
+                    // m_used = -inf (no visible key yet) the exponent -inf - -inf is NaN
+                    if (!(m_new > m_used[u] + thr_raw)) { m_new = m_used[u]; alpha = 1.0f; }
+                }
                 l_run[u] *= alpha;
 #pragma unroll
                 for (int cb = 0; cb < DV / 32; ++cb)
@@ -776,12 +893,19 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
                 m_used[u] = m_new;
             }
             const float mc = m_used[u] * c;
+            // LOCAL: the exponent is (s - m_used) c, not fma(s, c, -fl(m_used c)): the score that set
+            // m_used then gets P = 2^0 = 1 exactly, where the fma leaves the product's rounding
+            // residue in every P of the row (harmless in O, which divides it out, but l of a query
+            // with one visible key must be 1 and its O that key's V, bit for bit).  A row with no
+            // visible key yet (m_used = -inf; all its scores are -inf) subtracts 0: P = 2^-inf = 0.
+            float msub = 0.0f;
+            if constexpr (LOCAL) msub = m_used[u] == kNegInf ? 0.0f : m_used[u];
             float ps[4];
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
                 for (int x = 0; x < 16; ++x) {
-                    const float arg = fmaf(sacc[u][kb][x], c, -mc);
+                    const float arg = LOCAL ? (sacc[u][kb][x] - msub) * c : fmaf(sacc[u][kb][x], c, -mc);
                     const float pv = (FA_FWD_ABL & 1) ? arg : exp2_fast(arg);
                     // first four seed the partial sums (no `0 + p` adds: without
                     // fast-math the compiler must keep them, -0 + 0 != -0)
@@ -823,10 +947,17 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
     FA_FWD_STAMP(1);
     int wlast = 0;   // causal: the key limit (query row + off) of the wave's last query, a scalar
     if constexpr (CAUSAL) wlast = qb * BM + (__builtin_amdgcn_readfirstlane(wave) + 1) * NQB * 32 - 1 + (Nk - N);
+    int wlo = 0, whi = 0;   // local: the first key of the wave's first query and the last key of its last query, scalars
+    if constexpr (LOCAL) {
+        wlo = qb * BM + __builtin_amdgcn_readfirstlane(wave) * NQB * 32 + (Nk - N) - p.wleft;
+        whi = qb * BM + (__builtin_amdgcn_readfirstlane(wave) + 1) * NQB * 32 - 1 + (Nk - N) + p.wright;
+    }
     for (int j = jt0; j < jt1; j += 2) {
         gload(min(j + 1, jt1 - 1));
         if constexpr (CAUSAL) {   // only if some query of the wave sees the tile (wave-uniform)
             if (j * BN <= wlast) compute(buf0, buf0 + KBYTES, j);
+        } else if constexpr (LOCAL) {   // ... on both sides
+            if (j * BN <= whi && j * BN + BN - 1 >= wlo) compute(buf0, buf0 + KBYTES, j);
         } else {
             compute(buf0, buf0 + KBYTES, j);
         }
@@ -836,6 +967,8 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
             gload(min(j + 2, jt1 - 1));
             if constexpr (CAUSAL) {
                 if ((j + 1) * BN <= wlast) compute(buf1, buf1 + KBYTES, j + 1);
+            } else if constexpr (LOCAL) {
+                if ((j + 1) * BN <= whi && (j + 1) * BN + BN - 1 >= wlo) compute(buf1, buf1 + KBYTES, j + 1);
             } else {
                 compute(buf1, buf1 + KBYTES, j + 1);
             }
@@ -988,6 +1121,18 @@ __global__ __launch_bounds__(512, 1) void causal_fwd_w8q2_wide(FwdParams p) {
 template <class T, int D, int DV>
 __global__ __launch_bounds__(512, 1) void causal_fwd_w8b64_wide(FwdParams p) { dense_fwd_tiled<T, D, DV, 8, 64, 1, false, true, true>(p); }
 
+// local instantiations of the four default geometries (fa_local_fwd; no split-KV, no fa_fwd_p4)
+template <class T, int D, int DV>
+__global__ __launch_bounds__(512, 1) void local_fwd_w8b64(FwdParams p) { dense_fwd_tiled<T, D, DV, 8, 64, 1, false, false, false, true>(p); }
+template <class T, int D, int DV>
+__global__ __launch_bounds__(512, 1) void local_fwd_w8q2(FwdParams p) { dense_fwd_tiled<T, D, DV, 8, 64, 2, false, false, false, true>(p); }
+template <class T, int D, int DV>
+__global__ __launch_bounds__(512, 1) void local_fwd_w8q2_wide(FwdParams p) {
+    dense_fwd_tiled<T, D, DV, 8, 64, 2, false, (D <= 64 && DV <= 64), false, true>(p);   // the launcher picks it only there
+}
+template <class T, int D, int DV>
+__global__ __launch_bounds__(512, 1) void local_fwd_w8b64_wide(FwdParams p) { dense_fwd_tiled<T, D, DV, 8, 64, 1, false, true, false, true>(p); }
+
 // Split-KV combine: O = Σ_s o_s·2^(c(m_s − m)) / Σ_s l_s·2^(c(m_s − m)), m = max_s m_s
 // (fixed split order: deterministic).  One thread per output element.
 template <class T>
@@ -1038,26 +1183,36 @@ hipError_t launch_dense_fwd_p4(const FwdParams& p, int Dc, int dtype, dim3 grid,
 // The bf16 / fp16 kernel of a plan at head-dim classes (Dc, DVc).  Every kernel is
 // instantiated for the nine class pairs, the d = 128 forms of w8q2 included (a forced
 // kFwdW8Q2 reaches them), except the causal two-query-block kernels: d, dv <= 64 only (they
-// spill above, and the plan picks them only there).
+// spill above, and the plan picks them only there); the local ones likewise.
 template <class T>
 static hipError_t launch_16bit(const DenseFwdPlan& pl, const FwdParams& p, int Dc, int DVc, hipStream_t s) {
     const dim3 grid((unsigned)pl.grid), blk(pl.block);
-    const bool causal = pl.causal != 0;
-    auto go = [&](void (*kernel)(FwdParams)) { hipLaunchKernelGGL(kernel, grid, blk, 0, s, p); };
+    const bool causal = pl.causal != 0, local = pl.local;
+    typedef void (*Kernel)(FwdParams);
+    auto go = [&](Kernel kernel) { hipLaunchKernelGGL(kernel, grid, blk, 0, s, p); };
+    // the plan's kernel in its mask mode
+    auto mode = [&](Kernel dense, Kernel causal_k, Kernel local_k) { return local ? local_k : causal ? causal_k : dense; };
     hipError_t e = hipErrorInvalidValue;   // stays when a class or the kernel is not one of ours
     by_dim_class(Dc, [&](auto Dk) {
         by_dim_class(DVc, [&](auto DVk) {
             constexpr int D = decltype(Dk)::value, DV = decltype(DVk)::value;
             switch (pl.kernel) {
-                case kDenseFwdGeneric: go(causal ? dense_fwd_generic<T, D, DV, true> : dense_fwd_generic<T, D, DV>); break;
-                case kDenseFwdW8B64: go(causal ? causal_fwd_w8b64<T, D, DV> : dense_fwd_w8b64<T, D, DV>); break;
-                case kDenseFwdW8B64Wide: go(causal ? causal_fwd_w8b64_wide<T, D, DV> : dense_fwd_w8b64_wide<T, D, DV>); break;
+                case kDenseFwdGeneric:
+                    go(mode(dense_fwd_generic<T, D, DV>, dense_fwd_generic<T, D, DV, true>, dense_fwd_generic<T, D, DV, false, true>));
+                    break;
+                case kDenseFwdW8B64: go(mode(dense_fwd_w8b64<T, D, DV>, causal_fwd_w8b64<T, D, DV>, local_fwd_w8b64<T, D, DV>)); break;
+                case kDenseFwdW8B64Wide:
+                    go(mode(dense_fwd_w8b64_wide<T, D, DV>, causal_fwd_w8b64_wide<T, D, DV>, local_fwd_w8b64_wide<T, D, DV>));
+                    break;
                 case kDenseFwdW8Q2:
-                    if constexpr (D <= 64 && DV <= 64) go(causal ? causal_fwd_w8q2<T, D, DV> : dense_fwd_w8q2<T, D, DV>);
+                    if constexpr (D <= 64 && DV <= 64) go(mode(dense_fwd_w8q2<T, D, DV>, causal_fwd_w8q2<T, D, DV>, local_fwd_w8q2<T, D, DV>));
+                    else if (local) return;   // never planned: the local two-query-block kernels exist at d, dv <= 64 only
                     else go(dense_fwd_w8q2<T, D, DV>);
                     break;
                 case kDenseFwdW8Q2Wide:
-                    if constexpr (D <= 64 && DV <= 64) go(causal ? causal_fwd_w8q2_wide<T, D, DV> : dense_fwd_w8q2_wide<T, D, DV>);
+                    if constexpr (D <= 64 && DV <= 64)
+                        go(mode(dense_fwd_w8q2_wide<T, D, DV>, causal_fwd_w8q2_wide<T, D, DV>, local_fwd_w8q2_wide<T, D, DV>));
+                    else if (local) return;
                     else go(dense_fwd_w8q2_wide<T, D, DV>);
                     break;
                 case kDenseFwdW8B64Split: go(dense_fwd_w8b64_split<T, D, DV>); break;
@@ -1078,7 +1233,9 @@ static hipError_t launch_f32(const DenseFwdPlan& pl, const FwdParams& p, int Dc,
     by_dim_class(Dc, [&](auto Dk) {
         by_dim_class(DVc, [&](auto DVk) {
             constexpr int D = decltype(Dk)::value, DV = decltype(DVk)::value;
-            void (*kernel)(FwdParams) = pl.causal ? dense_fwd_generic_f32<D, DV, true> : dense_fwd_generic_f32<D, DV>;
+            void (*kernel)(FwdParams) = pl.local    ? dense_fwd_generic_f32<D, DV, false, true>
+                                        : pl.causal ? dense_fwd_generic_f32<D, DV, true>
+                                                    : dense_fwd_generic_f32<D, DV>;
             hipLaunchKernelGGL(kernel, dim3((unsigned)pl.grid), dim3(pl.block), 0, s, p);
             e = hipGetLastError();
         });
@@ -1095,11 +1252,15 @@ static void pad_keys(const void* src, void* dst, int64_t Nk, int64_t ldk, int64_
 // The shape's own needs (aligned tensors, the auto variant, room for everything): the
 // queries have no pointers, and the CU count does not change the total.
 size_t dense_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    return dense_fwd_plan(dtype, N, Nk, d, dv, batch, false, {kFwdAuto, 0}, true, true, SIZE_MAX, 0).total;
+    return dense_fwd_plan(dtype, N, Nk, d, dv, batch, kMaskNone, {kFwdAuto, 0}, true, true, SIZE_MAX, 0).total;
 }
 // fa_causal_fwd: the padded K / V copies only (causal launches never split the keys)
 size_t causal_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    return dense_fwd_plan(dtype, N, Nk, d, dv, batch, true, {kFwdAuto, 0}, true, true, SIZE_MAX, 0).total;
+    return dense_fwd_plan(dtype, N, Nk, d, dv, batch, kMaskCausal, {kFwdAuto, 0}, true, true, SIZE_MAX, 0).total;
+}
+// fa_local_fwd: the same, whatever the window (local launches never split either)
+size_t local_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
+    return dense_fwd_plan(dtype, N, Nk, d, dv, batch, kMaskLocal, {kFwdAuto, 0}, true, true, SIZE_MAX, 0).total;
 }
 
 int launch_dense_fwd(const DenseArgs& a, hipStream_t s, const char** why) {
@@ -1112,6 +1273,10 @@ int launch_dense_fwd(const DenseArgs& a, hipStream_t s, const char** why) {
     }
     if (a.causal && a.Nk < a.N) {
         *why = "causal attention needs Nk >= N (a query would see no key)";
+        return FA_ERR_UNSUPPORTED;
+    }
+    if (a.local && a.Nk < a.N) {
+        *why = "local attention needs Nk >= N (a query would see no key)";
         return FA_ERR_UNSUPPORTED;
     }
     if (a.N > INT32_MAX / 2 || a.Nk > INT32_MAX / 2 || a.N * a.d > INT32_MAX ||
@@ -1127,7 +1292,7 @@ int launch_dense_fwd(const DenseArgs& a, hipStream_t s, const char** why) {
         *why = "unknown dtype";
         return FA_ERR_INVALID_ARG;
     }
-    const DenseFwdPlan pl = dense_fwd_plan(a.dtype, a.N, a.Nk, a.d, a.dv, a.batch, a.causal != 0,
+    const DenseFwdPlan pl = dense_fwd_plan(a.dtype, a.N, a.Nk, a.d, a.dv, a.batch, dense_mask(a.causal, a.local),
                                            {g_fwd_variant, g_causal_rev}, aligned16(a.K) && aligned16(a.V),
                                            aligned16(a.Q) && aligned16(a.O), a.workspace ? a.workspace_bytes : 0,
                                            device_cus(s));
@@ -1143,6 +1308,10 @@ int launch_dense_fwd(const DenseArgs& a, hipStream_t s, const char** why) {
     p.rescale_log2 = g_fwd_rescale_log2;
     p.batch = (int)a.batch;
     p.nsplit = pl.nsplit; p.tps = pl.tps; p.opart = p.lpart = p.mpart = nullptr;
+    if (pl.local) {   // never split: the window rides in the split's two ints (fa_fwd_params.h)
+        p.wleft = local_clamp(a.left, a.Nk);
+        p.wright = local_clamp(a.right, a.Nk);
+    }
     p.causal = pl.causal;
     p.fast = pl.kv_vec;
     p.wide = pl.wide;

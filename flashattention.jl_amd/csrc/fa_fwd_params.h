@@ -1,5 +1,8 @@
 // fa_fwd_params.h — launch parameters of the dense forward kernels
-// (fa_fwd.hip: generic / tiled / split-KV kernels).
+// (fa_fwd.hip: generic / tiled / split-KV kernels).  The struct is pinned at 136 bytes with
+// no padding left, so the local (sliding-window) launches carry their clamped window in the
+// two split-KV ints, which they never use (anonymous unions below), rather than in a params
+// type of their own.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -19,7 +22,13 @@ struct FwdParams {
     // split-KV (small grids): nsplit key ranges of tps tiles each; partial results
     // (fp32, unnormalised, relative to the split's max) go to opart / lpart / mpart,
     // indexed by (split * batch + b)
-    int nsplit, tps, batch;
+    // Local (sliding-window) launches never split the keys, so their clamped window rides in
+    // these two ints (the struct has no padding left for new fields): wleft / wright, each in
+    // [0, Nk], Nk meaning no bound on that side (fa_local_fwd; read by the LOCAL
+    // instantiations only, which never read nsplit / tps / the partial pointers).
+    union { int nsplit; int wleft; };
+    union { int tps; int wright; };
+    int batch;
     float *opart, *lpart, *mpart;
     float scale, scale_log2;
     float rescale_log2;   // lazy-rescale threshold (log2 units): kRescaleLog2, or the debug knob

@@ -21,6 +21,10 @@ struct DenseArgs {
     size_t workspace_bytes = 0;
     double scale64 = 0.0;      // Float64 kernels: τ resolved in double (0: use scale)
     int causal = 0;            // fa_causal_fwd: query i sees keys j <= i + (Nk - N); 0: dense
+    // fa_local_fwd (never with causal): query i sees keys i + off - left <= j <= i + off + right,
+    // off = Nk - N; a negative side is unbounded (the launchers clamp: local_clamp)
+    int local = 0;
+    int64_t left = -1, right = -1;
 };
 
 struct DenseBwdArgs {
@@ -34,6 +38,8 @@ struct DenseBwdArgs {
     size_t workspace_bytes;
     double scale64 = 0.0;      // Float64 kernels: τ resolved in double (0: use scale)
     int causal = 0;            // fa_causal_bwd: as DenseArgs::causal (always the two-pass form)
+    int local = 0;             // fa_local_bwd: as DenseArgs::local (always the two-pass form)
+    int64_t left = -1, right = -1;
 };
 
 struct WindowGeom {
@@ -114,6 +120,9 @@ int launch_dense_bwd(const DenseBwdArgs& a, hipStream_t s, const char** why);
 // pass's running sums).  Neither asks the device.
 size_t causal_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch);
 size_t causal_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch);
+// local (DenseArgs / DenseBwdArgs with local = 1): the causal answers, whatever the window
+size_t local_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch);
+size_t local_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch);
 int dense_bwd_handoff_status(const void* workspace, size_t workspace_bytes, hipStream_t s, int* status,
                              const char** why);
 // Float64 (fa_f64.hip): the forward, and the backward's row statistics in double
@@ -159,6 +168,14 @@ inline int head_dim_class(int64_t d) {
 }
 
 constexpr int kMaxHeadDim = 128;
+
+// The mask of a dense-family launch: which instantiation of every kernel family runs.
+enum DenseMask : int { kMaskNone = 0, kMaskCausal = 1, kMaskLocal = 2 };
+inline DenseMask dense_mask(int causal, int local) { return local ? kMaskLocal : causal ? kMaskCausal : kMaskNone; }
+// One side of a local window as the kernels take it: in [0, Nk], where Nk binds nowhere
+// (negative = unbounded, and a value >= Nk is the same).  Done on the 64-bit value, before
+// anything becomes a 32-bit int.
+inline int local_clamp(int64_t w, int64_t Nk) { return (int)(w < 0 || w > Nk ? Nk : w); }
 
 // Workspace regions start on 256-B boundaries; the vector paths want 16-B aligned tensors.
 inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }

@@ -42,6 +42,7 @@ __all__ = [
     "windowed_fa_backward", "window_geometry", "circulant_fa", "circulant_fa_", "circulant_fa_backward",
     "circulant_dpa",
     "causal_fa", "causal_fa_", "causal_fa_backward", "causal_dpa",
+    "local_fa", "local_fa_", "local_fa_backward", "local_dpa",
     "fused_softmax", "fused_softmax_", "DTYPES",
 ]
 
@@ -154,6 +155,22 @@ def lib() -> ctypes.CDLL:
                                     i64, i64, i64, i64, i64, f32, vp, ctypes.c_size_t, vp]
         L.fa_debug_set_causal_order.restype = ctypes.c_int
         L.fa_debug_set_causal_order.argtypes = [ctypes.c_int]
+    if hasattr(L, "fa_local_fwd"):
+        for wq in (L.fa_local_fwd_workspace, L.fa_local_bwd_workspace):
+            wq.restype = ctypes.c_size_t
+            wq.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64]
+        L.fa_local_fwd.restype = ctypes.c_int
+        L.fa_local_fwd.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, f32, vp,
+                                   ctypes.c_size_t, vp]
+        L.fa_local_bwd.restype = ctypes.c_int
+        L.fa_local_bwd.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                   i64, i64, i64, i64, i64, i64, i64, f32, vp, ctypes.c_size_t, vp]
+        L.fa_debug_local_fwd_plan.restype = ctypes.c_int
+        L.fa_debug_local_fwd_plan.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(i64)]
+        L.fa_debug_local_bwd_plan.restype = ctypes.c_int
+        L.fa_debug_local_bwd_plan.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64, ctypes.c_int,
+                                              ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(i64)]
     L.fa_softmax_workspace.restype = ctypes.c_size_t
     L.fa_softmax_workspace.argtypes = [i64, i64, i64, ctypes.c_int]
     L.fa_softmax.restype = ctypes.c_int
@@ -426,6 +443,113 @@ def causal_dpa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float =
     return O, P
 
 
+# ----------------------------------------------------------------------------
+# local (sliding window around the causal diagonal)
+# ----------------------------------------------------------------------------
+def _local_extents(N: int, Nk: int) -> None:
+    """The C ABI's rule, raised before any device is touched."""
+    if Nk < N:
+        raise FlashAttentionError(FA_ERR_UNSUPPORTED,
+                                  f"local attention needs Nk >= N (got N = {N}, Nk = {Nk}): a query would see no key")
+
+
+def local_fa_(O: torch.Tensor, l: torch.Tensor, m: torch.Tensor,
+              Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor,
+              left: int, right: int, scale: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Sliding-window ``dense_fa!``, in place: with off = Nk - N, query i attends the keys
+    i + off - left <= j <= i + off + right (0 <= j < Nk).  A negative ``left`` / ``right``
+    means no bound on that side: (-1, 0) is :func:`causal_fa_`'s mask, (-1, -1)
+    :func:`dense_fa_`'s, (0, 0) one key per query.  Shapes as :func:`causal_fa_`; l, m
+    float32 over the visible keys.  Nk < N raises FlashAttentionError (unsupported)."""
+    for t in (O, l, m, Q, K, V):
+        _require(t.dim() == 3, "local_fa! expects 3-D (N, d, batch) arrays")
+    N, d, B = Q.shape
+    Nk, dv = K.shape[0], V.shape[1]
+    _require(K.shape == (Nk, d, B), f"K has shape {tuple(K.shape)}, expected ({Nk}, {d}, {B})")
+    _require(V.shape == (Nk, dv, B), f"V has shape {tuple(V.shape)}, expected ({Nk}, {dv}, {B})")
+    _require(O.shape == (N, dv, B), f"O has shape {tuple(O.shape)}, expected ({N}, {dv}, {B})")
+    _require(l.shape == (N, 1, B) and m.shape == (N, 1, B), "l, m must be (N, 1, batch)")
+    _require(l.dtype == torch.float32 and m.dtype == torch.float32, "l, m must be float32")
+    code = _dtype_code(Q, K, V, O)
+    _local_extents(N, Nk)
+    _device_check(Q, K, V, O, l, m)
+    Lb = lib()
+    nws = Lb.fa_local_fwd_workspace(code, N, Nk, d, dv, B)
+    ws = _workspace(Q.device, nws) if nws else None
+    _check(Lb.fa_local_fwd(code, _ptr(Q), _ptr(K), _ptr(V), _ptr(O), _ptr(l), _ptr(m),
+                           N, Nk, d, dv, B, int(left), int(right), float(scale), _ptr(ws), int(nws), _stream(Q)))
+    return O, l, m
+
+
+def local_fa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, left: int, right: int, scale: float = 0.0):
+    """``local_fa(q, k, v, left, right) -> (O, l, m)``: :func:`local_fa_` on fresh outputs.
+    q (N, d, B), k (Nk, d, B), v (Nk, dv, B) with Nk >= N."""
+    _require(q.dim() == 3 and k.dim() == 3 and v.dim() == 3, "local_fa expects 3-D (N, d, batch) arrays")
+    N, d, B = q.shape
+    O = jl_empty((N, v.shape[1], B), q.dtype, q.device)
+    l = jl_empty((N, 1, B), torch.float32, q.device)
+    m = jl_empty((N, 1, B), torch.float32, q.device)
+    return local_fa_(O, l, m, q, k, v, left, right, scale)
+
+
+def local_fa_backward(Q, K, V, O, dO, l, m, left: int, right: int, scale: float = 0.0):
+    """Backward of :func:`local_fa` for the same window: returns ``(dQ, dK, dV)``.  O, l, m
+    are the forward's outputs.  Always the two-pass form, so all three gradients are bitwise
+    reproducible; keys that no query sees get dK = dV = 0."""
+    for t in (Q, K, V, O, dO, l, m):
+        _require(t.dim() == 3, "local_fa_backward expects 3-D (N, d, batch) arrays")
+    N, d, B = Q.shape
+    Nk, dv = K.shape[0], V.shape[1]
+    _require(K.shape == (Nk, d, B) and V.shape == (Nk, dv, B), "K, V shapes disagree with Q")
+    _require(O.shape == (N, dv, B) and dO.shape == (N, dv, B), "O, dO must be (N, dv, batch)")
+    _require(l.shape == (N, 1, B) and m.shape == (N, 1, B), "l, m must be (N, 1, batch)")
+    _require(l.dtype == torch.float32 and m.dtype == torch.float32, "l, m must be float32")
+    code = _dtype_code(Q, K, V, O, dO)
+    _local_extents(N, Nk)
+    _device_check(Q, K, V, O, dO, l, m)
+    dQ = jl_empty((N, d, B), Q.dtype, Q.device)
+    dK = jl_empty((Nk, d, B), Q.dtype, Q.device)
+    dV = jl_empty((Nk, dv, B), Q.dtype, Q.device)
+    L = lib()
+    nws = L.fa_local_bwd_workspace(code, N, Nk, d, dv, B)
+    ws = _workspace(Q.device, nws, entry="local_fa_backward")
+    _check(L.fa_local_bwd(code, _ptr(Q), _ptr(K), _ptr(V), _ptr(O), _ptr(dO), _ptr(l), _ptr(m),
+                          _ptr(dQ), _ptr(dK), _ptr(dV), N, Nk, d, dv, B, int(left), int(right), float(scale),
+                          _ptr(ws), int(nws), _stream(Q)))
+    return dQ, dK, dV
+
+
+def local_dpa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, left: int, right: int, scale: float = 0.0):
+    """``local_dpa(q, k, v, left, right) -> (O, P)``: the materialising form of :func:`local_fa`,
+    in :func:`causal_dpa`'s style: S = τ Q Kᵀ by a library GEMM, −∞ outside the window,
+    P = softmax over the keys by this library's fa_softmax kernel (dims = 2; exactly 0 outside
+    the window), O = P V.  P is (N, Nk, B) in the input dtype; memory is O(N·Nk·B)."""
+    _require(q.dim() == 3 and k.dim() == 3 and v.dim() == 3, "local_dpa expects 3-D (N, d, batch) arrays")
+    N, d, B = q.shape
+    Nk, dv = k.shape[0], v.shape[1]
+    _require(k.shape == (Nk, d, B) and v.shape == (Nk, dv, B),
+             "DimensionMismatch: k must match q's feature and batch dims, v k's token count and the batch dim")
+    _dtype_code(q, k, v)
+    _local_extents(N, Nk)
+    _device_check(q, k, v)
+    tau = float(scale) if scale > 0 else 1.0 / math.sqrt(d)
+    Qr, Kr, Vr = _rm(q), _rm(k), _rm(v)       # [B][d][N], [B][d][Nk], [B][dv][Nk]
+    St = torch.bmm(Kr.transpose(1, 2), Qr)    # [B][Nk][N] = column-major (N, Nk, B): P's layout
+    St.mul_(tau)
+    j = torch.arange(Nk, device=q.device)[:, None]
+    c = torch.arange(N, device=q.device)[None, :] + (Nk - N)    # the causal diagonal's key of each query
+    hidden = torch.zeros((Nk, N), dtype=torch.bool, device=q.device)
+    if right >= 0:
+        hidden |= j > c + int(right)
+    if left >= 0:
+        hidden |= j < c - int(left)
+    St.masked_fill_(hidden[None], float("-inf"))
+    P = _rm(St)                               # (N, Nk, B) view
+    fused_softmax_(P, P, dims=2)
+    O = _rm(torch.bmm(Vr, St))                # [B][dv][N] = column-major (N, dv, B)
+    return O, P
+
+
 def circulant_fa_(O: torch.Tensor, l: torch.Tensor, m: torch.Tensor,
                   Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, W: int,
                   scale: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -561,7 +685,7 @@ def backward_handoff_status(device=None) -> int:
     stream = torch.cuda.current_stream(device)
     key = (device.type, device.index, stream.cuda_stream)
     buf = _WS.get(key)
-    _require(buf is not None and _WS_LAST.get(key) in ("dense_fa_backward", "causal_fa_backward"),
+    _require(buf is not None and _WS_LAST.get(key) in ("dense_fa_backward", "causal_fa_backward", "local_fa_backward"),
              "the last call that used this stream's scratch buffer was not dense_fa_backward")
     st = ctypes.c_int(-2)
     _check(lib().fa_dense_bwd_handoff_status(_ptr(buf), buf.numel(), ctypes.c_void_p(stream.cuda_stream),

@@ -349,6 +349,124 @@ function causal_fa_backward(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3}
     return causal_fa_backward_f32(Q, K, V, O, dO, Float32.(l), Float32.(m))
 end
 
+# local_fa!(O, l, m, Q, K, V, left, right) — sliding-window attention around the causal
+# diagonal (the reference has none): with off = Nk - N, query i attends the keys
+# i + off - left <= j <= i + off + right.  A negative left / right is unbounded on that side:
+# (-1, 0) is causal_fa!'s mask, (-1, -1) dense_fa!'s.  Nk < N is an error.
+function local_fa_f32!(O::ROCArray{T,3}, l::ROCArray{Float32,3}, m::ROCArray{Float32,3},
+                       Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3},
+                       left::Integer, right::Integer) where {T}
+    N, d, B = size(Q)
+    Nk, dv = size(K, 1), size(V, 2)
+    size(K) == (Nk, d, B) || throw(DimensionMismatch("K"))
+    size(V) == (Nk, dv, B) || throw(DimensionMismatch("V"))
+    size(O) == (N, dv, B) || throw(DimensionMismatch("O"))
+    size(l) == (N, 1, B) && size(m) == (N, 1, B) || throw(DimensionMismatch("l, m must be (N, 1, batch)"))
+    nws = ccall((:fa_local_fwd_workspace, libfa_hip), Csize_t,
+                (Cint, Int64, Int64, Int64, Int64, Int64), fa_dtype(T), N, Nk, d, dv, B)
+    with_workspace(nws) do ws
+        fa_check(ccall((:fa_local_fwd, libfa_hip), Cint,
+                       (Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32},
+                        Int64, Int64, Int64, Int64, Int64, Int64, Int64, Cfloat, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+                       fa_dtype(T), Q, K, V, O, l, m, N, Nk, d, dv, B, Int64(left), Int64(right), 0f0,
+                       ws, nws, stream_ptr()))
+    end
+    return O, l, m
+end
+
+# l, m in another element type, staged in Float32 as dense_fa_staged! does
+function local_fa_staged!(O::ROCArray{T,3}, l::ROCArray{S,3}, m::ROCArray{S,3},
+                          Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3},
+                          left::Integer, right::Integer) where {T,S}
+    size(l) == size(m) || throw(DimensionMismatch("l, m"))
+    lf, mf = similar(l, Float32), similar(m, Float32)
+    local_fa_f32!(O, lf, mf, Q, K, V, left, right)
+    l .= lf
+    m .= mf
+    return O, l, m
+end
+
+# The method set of causal_fa!, so that no call is ambiguous
+function local_fa!(O::ROCArray{T,3}, l::ROCArray{Float32,3}, m::ROCArray{Float32,3},
+                   Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3}, left::Integer, right::Integer) where {T}
+    return local_fa_f32!(O, l, m, Q, K, V, left, right)
+end
+function local_fa!(O::ROCArray{T,3}, l::ROCArray{T,3}, m::ROCArray{T,3},
+                   Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3}, left::Integer, right::Integer) where {T}
+    return local_fa_staged!(O, l, m, Q, K, V, left, right)
+end
+function local_fa!(O::ROCArray{Float32,3}, l::ROCArray{Float32,3}, m::ROCArray{Float32,3},
+                   Q::ROCArray{Float32,3}, K::ROCArray{Float32,3}, V::ROCArray{Float32,3},
+                   left::Integer, right::Integer)
+    return local_fa_f32!(O, l, m, Q, K, V, left, right)
+end
+function local_fa!(O::ROCArray{T,3}, l::ROCArray{S,3}, m::ROCArray{S,3},
+                   Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3}, left::Integer, right::Integer) where {T,S}
+    return local_fa_staged!(O, l, m, Q, K, V, left, right)
+end
+
+# local_fa(Q, K, V, left, right) -> (O, l, m), Float32 statistics
+function local_fa(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3}, left::Integer, right::Integer) where {T}
+    N, B = size(Q, 1), size(Q, 3)
+    O = similar(Q, N, size(V, 2), B)
+    l = similar(Q, Float32, N, 1, B)
+    m = similar(Q, Float32, N, 1, B)
+    return local_fa!(O, l, m, Q, K, V, left, right)
+end
+
+# local_fa_backward(Q, K, V, O, dO, l, m, left, right) -> (dQ, dK, dV): always the two-pass
+# form, all three gradients bitwise reproducible; keys no query sees get dK = dV = 0
+function local_fa_backward_f32(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3},
+                               O::ROCArray{T,3}, dO::ROCArray{T,3},
+                               l::ROCArray{Float32,3}, m::ROCArray{Float32,3},
+                               left::Integer, right::Integer) where {T}
+    N, d, B = size(Q)
+    Nk, dv = size(K, 1), size(V, 2)
+    size(K) == (Nk, d, B) && size(V) == (Nk, dv, B) ||
+        throw(DimensionMismatch("K, V shapes disagree with Q"))
+    size(O) == (N, dv, B) && size(dO) == (N, dv, B) ||
+        throw(DimensionMismatch("O, dO must be (N, dv, batch)"))
+    size(l) == (N, 1, B) && size(m) == (N, 1, B) ||
+        throw(DimensionMismatch("l, m must be (N, 1, batch)"))
+    dQ, dK, dV = similar(Q), similar(K), similar(V)
+    nws = ccall((:fa_local_bwd_workspace, libfa_hip), Csize_t,
+                (Cint, Int64, Int64, Int64, Int64, Int64), fa_dtype(T), N, Nk, d, dv, B)
+    with_workspace(nws) do ws
+        fa_check(ccall((:fa_local_bwd, libfa_hip), Cint,
+                       (Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float32},
+                        Ptr{Float32}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+                        Int64, Int64, Int64, Int64, Int64, Int64, Int64, Cfloat, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+                       fa_dtype(T), Q, K, V, O, dO, l, m, dQ, dK, dV, N, Nk, d, dv, B,
+                       Int64(left), Int64(right), 0f0, ws, nws, stream_ptr()))
+    end
+    return dQ, dK, dV
+end
+
+function local_fa_backward(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3},
+                           O::ROCArray{T,3}, dO::ROCArray{T,3},
+                           l::ROCArray{Float32,3}, m::ROCArray{Float32,3},
+                           left::Integer, right::Integer) where {T}
+    return local_fa_backward_f32(Q, K, V, O, dO, l, m, left, right)
+end
+function local_fa_backward(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3},
+                           O::ROCArray{T,3}, dO::ROCArray{T,3},
+                           l::ROCArray{T,3}, m::ROCArray{T,3},
+                           left::Integer, right::Integer) where {T}
+    return local_fa_backward_f32(Q, K, V, O, dO, Float32.(l), Float32.(m), left, right)
+end
+function local_fa_backward(Q::ROCArray{Float32,3}, K::ROCArray{Float32,3}, V::ROCArray{Float32,3},
+                           O::ROCArray{Float32,3}, dO::ROCArray{Float32,3},
+                           l::ROCArray{Float32,3}, m::ROCArray{Float32,3},
+                           left::Integer, right::Integer)
+    return local_fa_backward_f32(Q, K, V, O, dO, l, m, left, right)
+end
+function local_fa_backward(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3},
+                           O::ROCArray{T,3}, dO::ROCArray{T,3},
+                           l::ROCArray{S,3}, m::ROCArray{S,3},
+                           left::Integer, right::Integer) where {T,S}
+    return local_fa_backward_f32(Q, K, V, O, dO, Float32.(l), Float32.(m), left, right)
+end
+
 # windowed_fa(q, k, v, ws; stride, pad) — src/windowed.jl:3-23 (fused on the device)
 function windowed_fa(q::ROCArray{T,N}, k::ROCArray{T,N}, v::ROCArray{T,N}, windowsize;
                      stride=windowsize, pad=(windowsize - 1) ÷ 2) where {T,N}

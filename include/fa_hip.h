@@ -305,6 +305,63 @@ int fa_causal_bwd(int dtype,
                   float scale, void* workspace, size_t workspace_bytes,
                   void* hip_stream);
 
+/* Local (sliding-window) attention: a window (left, right) around the causal
+ * diagonal.  With off = Nk - N (bottom-right alignment, as fa_causal_fwd), query i
+ * attends the keys j with
+ *   0 <= j < Nk   and   i + off - left <= j <= i + off + right.
+ * left < 0 means no left bound, right < 0 no right bound, and a value >= Nk is the
+ * same as unbounded (both are int64_t and are clamped before any 32-bit use):
+ * (-1, 0) is fa_causal_fwd's mask, (-1, -1) fa_dense_fwd's, and (0, 0) lets query i
+ * see key i + off only.  Nk < N is FA_ERR_UNSUPPORTED; with Nk >= N the key i + off
+ * exists, so every query sees at least one key.  The mask is a select (score :=
+ * -Inf), never an added bias; l and m (float32 for every dtype) are taken over the
+ * visible keys.  Shapes, dtypes, head dims, ragged N / Nk, the order of the checks
+ * (null pointers, DimensionMismatch, head dims and Nk >= N, 32-bit extents,
+ * workspace; all before any launch) and the empty cases (N == 0 or batch == 0 is a
+ * no-op) are fa_causal_fwd's.  A local call always runs the local instantiations of
+ * the kernels, also for (-1, 0) and (-1, -1): the same tile bodies with the key loop
+ * cut on both sides per workgroup and per wave; never split-KV, never the
+ * one-wave-per-SIMD kernel. */
+int fa_local_fwd(int dtype,
+                 const void* Q, const void* K, const void* V,
+                 void* O, float* l, float* m,
+                 int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch,
+                 int64_t left, int64_t right,
+                 float scale, void* workspace, size_t workspace_bytes,
+                 void* hip_stream);
+
+/* Workspace bytes fa_local_fwd needs (0 is a valid answer): fa_causal_fwd_workspace's
+ * answer for the shape (the padded K / V copies only).  It depends on the shape
+ * alone, not on the window or the device. */
+size_t fa_local_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d,
+                              int64_t dv, int64_t batch);
+
+/* Workspace bytes fa_local_bwd needs: fa_causal_bwd_workspace's answer for the shape
+ * (header, row statistics, pad plan).  Independent of the window and the device. */
+size_t fa_local_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d,
+                              int64_t dv, int64_t batch);
+
+/* Local backward: the chain rule of fa_local_fwd over the visible keys (the
+ * formulas of fa_causal_bwd with P_ij = 0 outside the window).  O, l, m are
+ * fa_local_fwd's outputs for the same (left, right) (FA_DTYPE_F64 recomputes the
+ * statistics in double).  Always the two-pass form: a dQ pass over the key tiles
+ * between each block's first query's left edge and its last query's right edge, and
+ * a dK/dV pass over the queries j - off - right <= i <= j - off + left that see key
+ * j.  A key that no query sees (j < off - left: a KV cache longer than the window)
+ * gets dK = dV = 0, actually written: dQ, dK, dV are fully written, and all three are
+ * bitwise reproducible (no atomics, no hand-off).  The workspace header is written
+ * with plan 0, so fa_dense_bwd_handoff_status on this workspace answers -1.  Checks
+ * and empty inputs as fa_local_fwd. */
+int fa_local_bwd(int dtype,
+                 const void* Q, const void* K, const void* V,
+                 const void* O, const void* dO,
+                 const float* l, const float* m,
+                 void* dQ, void* dK, void* dV,
+                 int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch,
+                 int64_t left, int64_t right,
+                 float scale, void* workspace, size_t workspace_bytes,
+                 void* hip_stream);
+
 /* Standalone fused softmax, replaces
  *   fused_softmax!(P, S; dims)   reference src/fused_softmax.jl:1-41
  * (device versions src/cuda/fused_softmax.jl:11-314).  S, P: (M, N, batch)
