@@ -259,8 +259,17 @@ int fa_debug_win_bwd_plan(int dtype, int nspatial, const int64_t* spatial, int64
     return fa::win_bwd_plan(dtype, g, d, dv, batch, mode, in_aligned16 != 0, grad_aligned16 != 0, fa::win_cus(cus));
 }
 
-// Not part of the public header (tests): the plan of a dense (causal != 0: causal) forward /
-// backward, fa::dense_fwd_plan / fa::dense_bwd_plan (fa_dense_plan.h).  Returns the kernel, a
+// The argument checks the four plan hooks below share (mask: a fa::DenseMask value; a masked
+// plan needs Nk >= N; the backward plans also a head dimension within the compiled maximum).
+static bool plan_args_ok(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, int mask, bool bwd) {
+    return valid_dtype(dtype) && N >= 1 && Nk >= 1 && d >= 1 && dv >= 1 && batch >= 1 && mask >= fa::kMaskNone &&
+           mask <= fa::kMaskLocal && !(mask != fa::kMaskNone && Nk < N) &&
+           !(bwd && (d > fa::kMaxHeadDim || dv > fa::kMaxHeadDim));
+}
+
+// Not part of the public header (tests): the plan of a dense-family forward / backward,
+// fa::dense_fwd_plan / fa::dense_bwd_plan (fa_dense_plan.h); the argument `causal` is the
+// fa::DenseMask value (0 dense, 1 causal, 2 local).  Returns the kernel, a
 // fa::DenseFwdKernel / fa::DenseBwdKernel value (-1: invalid arguments, or a head dimension
 // above the compiled maximum), and writes the plan's other fields to out (may be null).
 // Every input is an argument, the knob values, the 16-B alignment facts, the workspace bytes
@@ -270,8 +279,8 @@ int fa_debug_win_bwd_plan(int dtype, int nspatial, const int64_t* spatial, int64
 int fa_debug_dense_fwd_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, int causal,
                             int variant, int causal_order, int kv_aligned16, int qo_aligned16, size_t ws_bytes,
                             int cus, int64_t* out) {
-    if (!valid_dtype(dtype) || N < 1 || Nk < 1 || d < 1 || dv < 1 || batch < 1 || (causal && Nk < N)) return -1;
-    const fa::DenseFwdPlan pl = fa::dense_fwd_plan(dtype, N, Nk, d, dv, batch, fa::dense_mask(causal, 0), {variant, causal_order},
+    if (!plan_args_ok(dtype, N, Nk, d, dv, batch, causal, false)) return -1;
+    const fa::DenseFwdPlan pl = fa::dense_fwd_plan(dtype, N, Nk, d, dv, batch, (fa::DenseMask)causal, {variant, causal_order},
                                                    kv_aligned16 != 0, qo_aligned16 != 0, ws_bytes, cus);
     if (out) {
         const int64_t f[17] = {pl.causal, pl.pad, pl.ldk, pl.nsplit, pl.tps, pl.rows, pl.nqb, pl.total_wg, pl.grid,
@@ -286,10 +295,8 @@ int fa_debug_dense_fwd_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t
 int fa_debug_dense_bwd_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, int causal,
                             int force_generic, int mode, int hoff, int xcd, int qkvdo_aligned16, size_t ws_bytes,
                             int cus, int64_t* out) {
-    if (!valid_dtype(dtype) || N < 1 || Nk < 1 || d < 1 || dv < 1 || batch < 1 || (causal && Nk < N) ||
-        d > fa::kMaxHeadDim || dv > fa::kMaxHeadDim)
-        return -1;
-    const fa::DenseBwdPlan pl = fa::dense_bwd_plan(dtype, N, Nk, d, dv, batch, fa::dense_mask(causal, 0),
+    if (!plan_args_ok(dtype, N, Nk, d, dv, batch, causal, true)) return -1;
+    const fa::DenseBwdPlan pl = fa::dense_bwd_plan(dtype, N, Nk, d, dv, batch, (fa::DenseMask)causal,
                                                    {force_generic, mode, hoff, xcd}, qkvdo_aligned16 != 0, ws_bytes, cus);
     if (out) {
         int64_t* o = out;
@@ -298,6 +305,32 @@ int fa_debug_dense_bwd_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t
             *o++ = v;
         for (size_t v : pl.off_slab) *o++ = (int64_t)v;
         for (size_t v : {pl.off_flags, pl.off_part, pl.flag_bytes, pl.total}) *o++ = (int64_t)v;
+    }
+    return pl.kernel;
+}
+// The plans of a local call under the default knobs, with fewer arguments and fields than the
+// two hooks above at mask 2 (which agree with them: tests/test_local_host.py).  The window is
+// not an argument: no plan depends on it.  forward out[8]: local, causal bits, pad, ldk,
+// nsplit, rows, grid, total; backward out[6]: padded, N, Nk, d, dv as run, total.
+int fa_debug_local_fwd_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch,
+                            int kv_aligned16, int qo_aligned16, size_t ws_bytes, int cus, int64_t* out) {
+    if (!plan_args_ok(dtype, N, Nk, d, dv, batch, fa::kMaskLocal, false)) return -1;
+    const fa::DenseFwdPlan pl = fa::dense_fwd_plan(dtype, N, Nk, d, dv, batch, fa::kMaskLocal, {fa::kFwdAuto, 0},
+                                                   kv_aligned16 != 0, qo_aligned16 != 0, ws_bytes, cus);
+    if (out) {
+        const int64_t f[8] = {pl.mask == fa::kMaskLocal, pl.causal, pl.pad, pl.ldk, pl.nsplit, pl.rows, pl.grid, (int64_t)pl.total};
+        for (int i = 0; i < 8; ++i) out[i] = f[i];
+    }
+    return pl.kernel;
+}
+int fa_debug_local_bwd_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch,
+                            int qkvdo_aligned16, size_t ws_bytes, int cus, int64_t* out) {
+    if (!plan_args_ok(dtype, N, Nk, d, dv, batch, fa::kMaskLocal, true)) return -1;
+    const fa::DenseBwdPlan pl = fa::dense_bwd_plan(dtype, N, Nk, d, dv, batch, fa::kMaskLocal,
+                                                   {0, fa::kBwdAuto, 3, -1}, qkvdo_aligned16 != 0, ws_bytes, cus);
+    if (out) {
+        const int64_t f[6] = {pl.padded, pl.N, pl.Nk, pl.d, pl.dv, (int64_t)pl.total};
+        for (int i = 0; i < 6; ++i) out[i] = f[i];
     }
     return pl.kernel;
 }
@@ -310,87 +343,196 @@ int fa_debug_set_win_bwd_grid(int v) {
     return old;
 }
 
+// ---------------------------------------------------------------------------------------
+// The dense family: dense, causal and local attention are one forward body, one backward
+// body and one workspace query under a fa::DenseMask.  The public functions below are
+// one-line forwards, and every place where the masks' contracts differ is an
+// `if (mask == fa::kMaskNone)` here or a name looked up from the mask.
+// ---------------------------------------------------------------------------------------
+
+// "workspace missing or smaller than fa_<mask>_<fwd|bwd>_workspace()": each mask names its own query
+static int fail_workspace(const char* fn, fa::DenseMask mask, const char* dir) {
+    const std::string msg = std::string("workspace missing or smaller than fa_") + fa::mask_word(mask) + "_" + dir + "_workspace()";
+    return fail(FA_ERR_WORKSPACE, fn, msg.c_str());
+}
+
+// The checks the causal and local entry points make after the null-pointer and DimensionMismatch
+// ones, in order: head dims and Nk >= N, then the kernels' 32-bit extents (the launchers'
+// own conditions, repeated here so that they precede the workspace check and any launch).
+// The dense entry points make none: their launchers refuse, in their own words, after the
+// workspace check.
+static int masked_shape_check(fa::DenseMask mask, int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv,
+                              int64_t batch, bool bwd, const char** why) {
+    if (mask == fa::kMaskNone) return FA_OK;
+    if (d > fa::kMaxHeadDim || dv > fa::kMaxHeadDim) {
+        *why = "head dimension exceeds the compiled maximum (128)";
+        return FA_ERR_UNSUPPORTED;
+    }
+    if (fa::mask_lacks_keys(mask, N, Nk, why)) return FA_ERR_UNSUPPORTED;
+    const bool big = N > INT32_MAX / 2 || Nk > INT32_MAX / 2 || N * d > INT32_MAX || Nk * d > INT32_MAX ||
+                     Nk * dv > INT32_MAX || N * dv > INT32_MAX ||
+                     (bwd && (N * batch > INT32_MAX / 2 || Nk * batch > INT32_MAX / 2)) ||
+                     (dtype == FA_DTYPE_F64 && (N + 63) / 64 * batch > INT32_MAX);
+    if (big) {
+        *why = "extent exceeds the kernels' 32-bit addressing";
+        return FA_ERR_UNSUPPORTED;
+    }
+    return FA_OK;
+}
+
+// The six workspace queries.  Dense answers 0 only for non-positive extents; a masked call
+// with Nk < N is refused, so its query answers 0 as well.
+static size_t dense_family_workspace(fa::DenseMask mask, bool bwd, int dtype, int64_t N, int64_t Nk, int64_t d,
+                                     int64_t dv, int64_t batch) {
+    if (!valid_dtype(dtype) || N < 1 || Nk < (mask == fa::kMaskNone ? 1 : N) || d < 1 || dv < 1 || batch < 1) return 0;
+    return bwd ? fa::dense_bwd_workspace(dtype, N, Nk, d, dv, batch, mask)
+               : fa::dense_fwd_workspace(dtype, N, Nk, d, dv, batch, mask);
+}
+
+// fn: the public function's name.  The window (left, right) is read under kMaskLocal only; it
+// stays int64_t down to the launchers (fa::mask_ints clamps it to [0, Nk] before it becomes a
+// 32-bit int) and changes neither a check nor a workspace answer.  takes_ws: false for
+// fa_dense_fwd, which has no workspace argument and runs what needs none.
+static int dense_family_fwd(fa::DenseMask mask, const char* fn, int dtype, const void* Q, const void* K,
+                            const void* V, void* O, float* l, float* m, int64_t N, int64_t Nk, int64_t d,
+                            int64_t dv, int64_t batch, int64_t left, int64_t right, float scale, bool takes_ws,
+                            void* workspace, size_t workspace_bytes, void* hip_stream) {
+    if (!valid_dtype(dtype)) return fail(FA_ERR_INVALID_ARG, fn, "unknown dtype");
+    if (N < 0 || Nk < 0 || d < 1 || dv < 1 || batch < 0)
+        return fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: N, Nk, batch must be >= 0 and d, dv >= 1");
+    if (mask == fa::kMaskNone) {   // no query: nothing to write; no key: O = 0, l = 0, m = -Inf
+        int erc;
+        if (dense_fwd_empty(dtype, O, l, m, N, Nk, dv, batch, (hipStream_t)hip_stream, &erc))
+            return erc == FA_OK ? ok() : fail(erc, fn, erc == FA_ERR_HIP ? "hipMemsetAsync failed" : "null pointer");
+    } else if (N == 0 || batch == 0) {
+        return ok();   // no query: nothing to write (Nk = 0 < N is refused below)
+    }
+    if (!Q || !K || !V || !O || !l || !m) return fail(FA_ERR_INVALID_ARG, fn, "null pointer");
+    const char* why = "";
+    int rc = masked_shape_check(mask, dtype, N, Nk, d, dv, batch, false, &why);
+    if (rc != FA_OK) return fail(rc, fn, why);
+    if (takes_ws) {
+        const size_t need = fa::dense_fwd_workspace(dtype, N, Nk, d, dv, batch, mask);
+        if (need > 0 && (!workspace || workspace_bytes < need))
+            return fail_workspace(fn, mask, "fwd");
+    }
+    fa::DenseArgs a{dtype, Q, K, V, O, l, m, N, Nk, d, dv, batch, resolve_scale(scale, d)};
+    a.scale64 = resolve_scale64(scale, d);
+    a.workspace = workspace;
+    a.workspace_bytes = workspace_bytes;
+    a.mask = mask;
+    a.left = left;
+    a.right = right;
+    rc = fa::launch_dense_fwd(a, (hipStream_t)hip_stream, &why);
+    return rc == FA_OK ? ok() : fail(rc, fn, why);
+}
+
+static int dense_family_bwd(fa::DenseMask mask, const char* fn, int dtype, const void* Q, const void* K,
+                            const void* V, const void* O, const void* dO, const float* l, const float* m, void* dQ,
+                            void* dK, void* dV, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch,
+                            int64_t left, int64_t right, float scale, void* workspace, size_t workspace_bytes,
+                            void* hip_stream) {
+    if (!valid_dtype(dtype)) return fail(FA_ERR_INVALID_ARG, fn, "unknown dtype");
+    if (N < 0 || Nk < 0 || d < 1 || dv < 1 || batch < 0)
+        return fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: N, Nk, batch must be >= 0 and d, dv >= 1");
+    if (mask == fa::kMaskNone) {
+        if (N == 0 || Nk == 0 || batch == 0) {   // empty sums: every gradient element is 0
+            const size_t esz = fa::dtype_size(dtype);
+            const hipStream_t s = (hipStream_t)hip_stream;
+            const size_t nq = (size_t)(N * d * batch), nk = (size_t)(Nk * d * batch), nv = (size_t)(Nk * dv * batch);
+            if ((nq && !dQ) || (nk && (!dK || !dV))) return fail(FA_ERR_INVALID_ARG, fn, "null pointer");
+            if ((nq && hipMemsetAsync(dQ, 0, nq * esz, s) != hipSuccess) ||
+                (nk && hipMemsetAsync(dK, 0, nk * esz, s) != hipSuccess) ||
+                (nv && hipMemsetAsync(dV, 0, nv * esz, s) != hipSuccess))
+                return fail(FA_ERR_HIP, fn, "hipMemsetAsync failed");
+            return ok();
+        }
+    } else if (N == 0 || batch == 0) {
+        return ok();   // no query (and, with Nk >= N required, no call with keys only)
+    }
+    if (!Q || !K || !V || !O || !dO || !l || !m || !dQ || !dK || !dV)
+        return fail(FA_ERR_INVALID_ARG, fn, "null pointer");
+    const char* why = "";
+    int rc = masked_shape_check(mask, dtype, N, Nk, d, dv, batch, true, &why);
+    if (rc != FA_OK) return fail(rc, fn, why);
+    const size_t need = fa::dense_bwd_workspace(dtype, N, Nk, d, dv, batch, mask);
+    // a masked backward rejects a null workspace whatever `need` is
+    if ((mask != fa::kMaskNone || need > 0) && (!workspace || workspace_bytes < need))
+        return fail_workspace(fn, mask, "bwd");
+    fa::DenseBwdArgs a{dtype, Q, K, V, O, dO, l, m, dQ, dK, dV, N, Nk, d, dv, batch,
+                       resolve_scale(scale, d), workspace, workspace_bytes};
+    a.scale64 = resolve_scale64(scale, d);
+    a.mask = mask;
+    a.left = left;
+    a.right = right;
+    rc = fa::launch_dense_bwd(a, (hipStream_t)hip_stream, &why);
+    return rc == FA_OK ? ok() : fail(rc, fn, why);
+}
+
 size_t fa_dense_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    if (!valid_dtype(dtype) || N < 1 || Nk < 1 || d < 1 || dv < 1 || batch < 1) return 0;
-    return fa::dense_fwd_workspace(dtype, N, Nk, d, dv, batch);
+    return dense_family_workspace(fa::kMaskNone, false, dtype, N, Nk, d, dv, batch);
+}
+size_t fa_dense_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
+    return dense_family_workspace(fa::kMaskNone, true, dtype, N, Nk, d, dv, batch);
+}
+size_t fa_causal_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
+    return dense_family_workspace(fa::kMaskCausal, false, dtype, N, Nk, d, dv, batch);
+}
+size_t fa_causal_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
+    return dense_family_workspace(fa::kMaskCausal, true, dtype, N, Nk, d, dv, batch);
+}
+size_t fa_local_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
+    return dense_family_workspace(fa::kMaskLocal, false, dtype, N, Nk, d, dv, batch);
+}
+size_t fa_local_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
+    return dense_family_workspace(fa::kMaskLocal, true, dtype, N, Nk, d, dv, batch);
 }
 
 int fa_dense_fwd_ws(int dtype, const void* Q, const void* K, const void* V, void* O, float* l, float* m,
                     int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, float scale,
                     void* workspace, size_t workspace_bytes, void* hip_stream) {
-    static const char* fn = "fa_dense_fwd_ws";
-    if (!valid_dtype(dtype)) return fail(FA_ERR_INVALID_ARG, fn, "unknown dtype");
-    if (N < 0 || Nk < 0 || d < 1 || dv < 1 || batch < 0)
-        return fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: N, Nk, batch must be >= 0 and d, dv >= 1");
-    int erc;
-    if (dense_fwd_empty(dtype, O, l, m, N, Nk, dv, batch, (hipStream_t)hip_stream, &erc))
-        return erc == FA_OK ? ok() : fail(erc, fn, erc == FA_ERR_HIP ? "hipMemsetAsync failed" : "null pointer");
-    if (!Q || !K || !V || !O || !l || !m) return fail(FA_ERR_INVALID_ARG, fn, "null pointer");
-    const size_t need = fa::dense_fwd_workspace(dtype, N, Nk, d, dv, batch);
-    if (need > 0 && (!workspace || workspace_bytes < need))
-        return fail(FA_ERR_WORKSPACE, fn, "workspace missing or smaller than fa_dense_fwd_workspace()");
-    fa::DenseArgs a{dtype, Q, K, V, O, l, m, N, Nk, d, dv, batch, resolve_scale(scale, d)};
-    a.scale64 = resolve_scale64(scale, d);
-    a.workspace = workspace;
-    a.workspace_bytes = workspace_bytes;
-    const char* why = "";
-    const int rc = fa::launch_dense_fwd(a, (hipStream_t)hip_stream, &why);
-    return rc == FA_OK ? ok() : fail(rc, fn, why);
+    return dense_family_fwd(fa::kMaskNone, "fa_dense_fwd_ws", dtype, Q, K, V, O, l, m, N, Nk, d, dv, batch, -1, -1, scale,
+                            true, workspace, workspace_bytes, hip_stream);
 }
-
 int fa_dense_fwd(int dtype, const void* Q, const void* K, const void* V, void* O, float* l, float* m,
                  int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, float scale,
                  void* hip_stream) {
-    static const char* fn = "fa_dense_fwd";
-    if (!valid_dtype(dtype)) return fail(FA_ERR_INVALID_ARG, fn, "unknown dtype");
-    if (N < 0 || Nk < 0 || d < 1 || dv < 1 || batch < 0)
-        return fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: N, Nk, batch must be >= 0 and d, dv >= 1");
-    int erc;
-    if (dense_fwd_empty(dtype, O, l, m, N, Nk, dv, batch, (hipStream_t)hip_stream, &erc))
-        return erc == FA_OK ? ok() : fail(erc, fn, erc == FA_ERR_HIP ? "hipMemsetAsync failed" : "null pointer");
-    if (!Q || !K || !V || !O || !l || !m) return fail(FA_ERR_INVALID_ARG, fn, "null pointer");
-    fa::DenseArgs a{dtype, Q, K, V, O, l, m, N, Nk, d, dv, batch, resolve_scale(scale, d)};
-    a.scale64 = resolve_scale64(scale, d);
-    const char* why = "";
-    const int rc = fa::launch_dense_fwd(a, (hipStream_t)hip_stream, &why);
-    return rc == FA_OK ? ok() : fail(rc, fn, why);
+    return dense_family_fwd(fa::kMaskNone, "fa_dense_fwd", dtype, Q, K, V, O, l, m, N, Nk, d, dv, batch, -1, -1, scale,
+                            false, nullptr, 0, hip_stream);
 }
-
-size_t fa_dense_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    if (!valid_dtype(dtype) || N < 1 || Nk < 1 || d < 1 || dv < 1 || batch < 1) return 0;
-    return fa::dense_bwd_workspace(dtype, N, Nk, d, dv, batch);
+int fa_causal_fwd(int dtype, const void* Q, const void* K, const void* V, void* O, float* l, float* m,
+                  int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, float scale,
+                  void* workspace, size_t workspace_bytes, void* hip_stream) {
+    return dense_family_fwd(fa::kMaskCausal, "fa_causal_fwd", dtype, Q, K, V, O, l, m, N, Nk, d, dv, batch, -1, -1, scale,
+                            true, workspace, workspace_bytes, hip_stream);
+}
+int fa_local_fwd(int dtype, const void* Q, const void* K, const void* V, void* O, float* l, float* m,
+                 int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, int64_t left, int64_t right,
+                 float scale, void* workspace, size_t workspace_bytes, void* hip_stream) {
+    return dense_family_fwd(fa::kMaskLocal, "fa_local_fwd", dtype, Q, K, V, O, l, m, N, Nk, d, dv, batch, left, right,
+                            scale, true, workspace, workspace_bytes, hip_stream);
 }
 
 int fa_dense_bwd(int dtype, const void* Q, const void* K, const void* V, const void* O, const void* dO,
                  const float* l, const float* m, void* dQ, void* dK, void* dV, int64_t N, int64_t Nk,
                  int64_t d, int64_t dv, int64_t batch, float scale, void* workspace,
                  size_t workspace_bytes, void* hip_stream) {
-    static const char* fn = "fa_dense_bwd";
-    if (!valid_dtype(dtype)) return fail(FA_ERR_INVALID_ARG, fn, "unknown dtype");
-    if (N < 0 || Nk < 0 || d < 1 || dv < 1 || batch < 0)
-        return fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: N, Nk, batch must be >= 0 and d, dv >= 1");
-    if (N == 0 || Nk == 0 || batch == 0) {   // empty sums: every gradient element is 0
-        const size_t esz = fa::dtype_size(dtype);
-        const hipStream_t s = (hipStream_t)hip_stream;
-        const size_t nq = (size_t)(N * d * batch), nk = (size_t)(Nk * d * batch), nv = (size_t)(Nk * dv * batch);
-        if ((nq && !dQ) || (nk && (!dK || !dV))) return fail(FA_ERR_INVALID_ARG, fn, "null pointer");
-        if ((nq && hipMemsetAsync(dQ, 0, nq * esz, s) != hipSuccess) ||
-            (nk && hipMemsetAsync(dK, 0, nk * esz, s) != hipSuccess) ||
-            (nv && hipMemsetAsync(dV, 0, nv * esz, s) != hipSuccess))
-            return fail(FA_ERR_HIP, fn, "hipMemsetAsync failed");
-        return ok();
-    }
-    if (!Q || !K || !V || !O || !dO || !l || !m || !dQ || !dK || !dV)
-        return fail(FA_ERR_INVALID_ARG, fn, "null pointer");
-    const size_t need = fa::dense_bwd_workspace(dtype, N, Nk, d, dv, batch);
-    if (need > 0 && (!workspace || workspace_bytes < need))
-        return fail(FA_ERR_WORKSPACE, fn, "workspace missing or smaller than fa_dense_bwd_workspace()");
-    fa::DenseBwdArgs a{dtype, Q, K, V, O, dO, l, m, dQ, dK, dV, N, Nk, d, dv, batch,
-                       resolve_scale(scale, d), workspace, workspace_bytes};
-    a.scale64 = resolve_scale64(scale, d);
-    const char* why = "";
-    const int rc = fa::launch_dense_bwd(a, (hipStream_t)hip_stream, &why);
-    return rc == FA_OK ? ok() : fail(rc, fn, why);
+    return dense_family_bwd(fa::kMaskNone, "fa_dense_bwd", dtype, Q, K, V, O, dO, l, m, dQ, dK, dV, N, Nk, d, dv, batch,
+                            -1, -1, scale, workspace, workspace_bytes, hip_stream);
+}
+int fa_causal_bwd(int dtype, const void* Q, const void* K, const void* V, const void* O, const void* dO,
+                  const float* l, const float* m, void* dQ, void* dK, void* dV, int64_t N, int64_t Nk,
+                  int64_t d, int64_t dv, int64_t batch, float scale, void* workspace,
+                  size_t workspace_bytes, void* hip_stream) {
+    return dense_family_bwd(fa::kMaskCausal, "fa_causal_bwd", dtype, Q, K, V, O, dO, l, m, dQ, dK, dV, N, Nk, d, dv, batch,
+                            -1, -1, scale, workspace, workspace_bytes, hip_stream);
+}
+int fa_local_bwd(int dtype, const void* Q, const void* K, const void* V, const void* O, const void* dO,
+                 const float* l, const float* m, void* dQ, void* dK, void* dV, int64_t N, int64_t Nk,
+                 int64_t d, int64_t dv, int64_t batch, int64_t left, int64_t right, float scale,
+                 void* workspace, size_t workspace_bytes, void* hip_stream) {
+    return dense_family_bwd(fa::kMaskLocal, "fa_local_bwd", dtype, Q, K, V, O, dO, l, m, dQ, dK, dV, N, Nk, d, dv, batch,
+                            left, right, scale, workspace, workspace_bytes, hip_stream);
 }
 
 // Not part of the public header: launch order of the causal fast forward's query blocks
@@ -403,196 +545,6 @@ int fa_debug_set_causal_order(int v) {
     if (v < 0 || v > 2) return -2;
     fa::g_causal_rev = v;
     return old;
-}
-
-// The checks fa_causal_fwd / fa_causal_bwd share after the null-pointer and DimensionMismatch
-// ones, in order: head dims and Nk >= N, then the kernels' 32-bit extents (the launchers'
-// own conditions, repeated here so that they precede the workspace check and any launch).
-static int causal_shape_check(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch,
-                              bool bwd, const char** why) {
-    if (d > fa::kMaxHeadDim || dv > fa::kMaxHeadDim) {
-        *why = "head dimension exceeds the compiled maximum (128)";
-        return FA_ERR_UNSUPPORTED;
-    }
-    if (Nk < N) {
-        *why = "causal attention needs Nk >= N (a query would see no key)";
-        return FA_ERR_UNSUPPORTED;
-    }
-    const bool big = N > INT32_MAX / 2 || Nk > INT32_MAX / 2 || N * d > INT32_MAX || Nk * d > INT32_MAX ||
-                     Nk * dv > INT32_MAX || N * dv > INT32_MAX ||
-                     (bwd && (N * batch > INT32_MAX / 2 || Nk * batch > INT32_MAX / 2)) ||
-                     (dtype == FA_DTYPE_F64 && (N + 63) / 64 * batch > INT32_MAX);
-    if (big) {
-        *why = "extent exceeds the kernels' 32-bit addressing";
-        return FA_ERR_UNSUPPORTED;
-    }
-    return FA_OK;
-}
-
-size_t fa_causal_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    if (!valid_dtype(dtype) || N < 1 || Nk < N || d < 1 || dv < 1 || batch < 1) return 0;
-    return fa::causal_fwd_workspace(dtype, N, Nk, d, dv, batch);
-}
-
-int fa_causal_fwd(int dtype, const void* Q, const void* K, const void* V, void* O, float* l, float* m,
-                  int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, float scale,
-                  void* workspace, size_t workspace_bytes, void* hip_stream) {
-    static const char* fn = "fa_causal_fwd";
-    if (!valid_dtype(dtype)) return fail(FA_ERR_INVALID_ARG, fn, "unknown dtype");
-    if (N < 0 || Nk < 0 || d < 1 || dv < 1 || batch < 0)
-        return fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: N, Nk, batch must be >= 0 and d, dv >= 1");
-    if (N == 0 || batch == 0) return ok();   // no query: nothing to write
-    if (!Q || !K || !V || !O || !l || !m) return fail(FA_ERR_INVALID_ARG, fn, "null pointer");
-    const char* why = "";
-    int rc = causal_shape_check(dtype, N, Nk, d, dv, batch, false, &why);
-    if (rc != FA_OK) return fail(rc, fn, why);
-    const size_t need = fa::causal_fwd_workspace(dtype, N, Nk, d, dv, batch);
-    if (need > 0 && (!workspace || workspace_bytes < need))
-        return fail(FA_ERR_WORKSPACE, fn, "workspace missing or smaller than fa_causal_fwd_workspace()");
-    fa::DenseArgs a{dtype, Q, K, V, O, l, m, N, Nk, d, dv, batch, resolve_scale(scale, d)};
-    a.scale64 = resolve_scale64(scale, d);
-    a.workspace = workspace;
-    a.workspace_bytes = workspace_bytes;
-    a.causal = 1;
-    rc = fa::launch_dense_fwd(a, (hipStream_t)hip_stream, &why);
-    return rc == FA_OK ? ok() : fail(rc, fn, why);
-}
-
-size_t fa_causal_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    if (!valid_dtype(dtype) || N < 1 || Nk < N || d < 1 || dv < 1 || batch < 1) return 0;
-    return fa::causal_bwd_workspace(dtype, N, Nk, d, dv, batch);
-}
-
-int fa_causal_bwd(int dtype, const void* Q, const void* K, const void* V, const void* O, const void* dO,
-                  const float* l, const float* m, void* dQ, void* dK, void* dV, int64_t N, int64_t Nk,
-                  int64_t d, int64_t dv, int64_t batch, float scale, void* workspace,
-                  size_t workspace_bytes, void* hip_stream) {
-    static const char* fn = "fa_causal_bwd";
-    if (!valid_dtype(dtype)) return fail(FA_ERR_INVALID_ARG, fn, "unknown dtype");
-    if (N < 0 || Nk < 0 || d < 1 || dv < 1 || batch < 0)
-        return fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: N, Nk, batch must be >= 0 and d, dv >= 1");
-    if (N == 0 || batch == 0) return ok();   // no query (and, with Nk >= N required, no call with keys only)
-    if (!Q || !K || !V || !O || !dO || !l || !m || !dQ || !dK || !dV)
-        return fail(FA_ERR_INVALID_ARG, fn, "null pointer");
-    const char* why = "";
-    int rc = causal_shape_check(dtype, N, Nk, d, dv, batch, true, &why);
-    if (rc != FA_OK) return fail(rc, fn, why);
-    const size_t need = fa::causal_bwd_workspace(dtype, N, Nk, d, dv, batch);
-    if (!workspace || workspace_bytes < need)
-        return fail(FA_ERR_WORKSPACE, fn, "workspace missing or smaller than fa_causal_bwd_workspace()");
-    fa::DenseBwdArgs a{dtype, Q, K, V, O, dO, l, m, dQ, dK, dV, N, Nk, d, dv, batch,
-                       resolve_scale(scale, d), workspace, workspace_bytes};
-    a.scale64 = resolve_scale64(scale, d);
-    a.causal = 1;
-    rc = fa::launch_dense_bwd(a, (hipStream_t)hip_stream, &why);
-    return rc == FA_OK ? ok() : fail(rc, fn, why);
-}
-
-// fa_local_fwd / fa_local_bwd: the causal pair's contract (the same checks in the same order,
-// the same workspace totals) with the window (left, right) around the causal diagonal.  The
-// window stays int64_t down to the launchers, which clamp it to [0, Nk] (fa::local_clamp)
-// before it becomes a 32-bit int; it changes neither a check nor a workspace answer.
-static int local_shape_check(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, bool bwd,
-                             const char** why) {
-    if (d <= fa::kMaxHeadDim && dv <= fa::kMaxHeadDim && Nk < N) {
-        *why = "local attention needs Nk >= N (a query would see no key)";
-        return FA_ERR_UNSUPPORTED;
-    }
-    return causal_shape_check(dtype, N, Nk, d, dv, batch, bwd, why);
-}
-
-size_t fa_local_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    if (!valid_dtype(dtype) || N < 1 || Nk < N || d < 1 || dv < 1 || batch < 1) return 0;
-    return fa::local_fwd_workspace(dtype, N, Nk, d, dv, batch);
-}
-
-int fa_local_fwd(int dtype, const void* Q, const void* K, const void* V, void* O, float* l, float* m,
-                 int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, int64_t left, int64_t right,
-                 float scale, void* workspace, size_t workspace_bytes, void* hip_stream) {
-    static const char* fn = "fa_local_fwd";
-    if (!valid_dtype(dtype)) return fail(FA_ERR_INVALID_ARG, fn, "unknown dtype");
-    if (N < 0 || Nk < 0 || d < 1 || dv < 1 || batch < 0)
-        return fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: N, Nk, batch must be >= 0 and d, dv >= 1");
-    if (N == 0 || batch == 0) return ok();   // no query: nothing to write
-    if (!Q || !K || !V || !O || !l || !m) return fail(FA_ERR_INVALID_ARG, fn, "null pointer");
-    const char* why = "";
-    int rc = local_shape_check(dtype, N, Nk, d, dv, batch, false, &why);
-    if (rc != FA_OK) return fail(rc, fn, why);
-    const size_t need = fa::local_fwd_workspace(dtype, N, Nk, d, dv, batch);
-    if (need > 0 && (!workspace || workspace_bytes < need))
-        return fail(FA_ERR_WORKSPACE, fn, "workspace missing or smaller than fa_local_fwd_workspace()");
-    fa::DenseArgs a{dtype, Q, K, V, O, l, m, N, Nk, d, dv, batch, resolve_scale(scale, d)};
-    a.scale64 = resolve_scale64(scale, d);
-    a.workspace = workspace;
-    a.workspace_bytes = workspace_bytes;
-    a.local = 1;
-    a.left = left;
-    a.right = right;
-    rc = fa::launch_dense_fwd(a, (hipStream_t)hip_stream, &why);
-    return rc == FA_OK ? ok() : fail(rc, fn, why);
-}
-
-size_t fa_local_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    if (!valid_dtype(dtype) || N < 1 || Nk < N || d < 1 || dv < 1 || batch < 1) return 0;
-    return fa::local_bwd_workspace(dtype, N, Nk, d, dv, batch);
-}
-
-int fa_local_bwd(int dtype, const void* Q, const void* K, const void* V, const void* O, const void* dO,
-                 const float* l, const float* m, void* dQ, void* dK, void* dV, int64_t N, int64_t Nk,
-                 int64_t d, int64_t dv, int64_t batch, int64_t left, int64_t right, float scale,
-                 void* workspace, size_t workspace_bytes, void* hip_stream) {
-    static const char* fn = "fa_local_bwd";
-    if (!valid_dtype(dtype)) return fail(FA_ERR_INVALID_ARG, fn, "unknown dtype");
-    if (N < 0 || Nk < 0 || d < 1 || dv < 1 || batch < 0)
-        return fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: N, Nk, batch must be >= 0 and d, dv >= 1");
-    if (N == 0 || batch == 0) return ok();   // no query (and, with Nk >= N required, no call with keys only)
-    if (!Q || !K || !V || !O || !dO || !l || !m || !dQ || !dK || !dV)
-        return fail(FA_ERR_INVALID_ARG, fn, "null pointer");
-    const char* why = "";
-    int rc = local_shape_check(dtype, N, Nk, d, dv, batch, true, &why);
-    if (rc != FA_OK) return fail(rc, fn, why);
-    const size_t need = fa::local_bwd_workspace(dtype, N, Nk, d, dv, batch);
-    if (!workspace || workspace_bytes < need)
-        return fail(FA_ERR_WORKSPACE, fn, "workspace missing or smaller than fa_local_bwd_workspace()");
-    fa::DenseBwdArgs a{dtype, Q, K, V, O, dO, l, m, dQ, dK, dV, N, Nk, d, dv, batch,
-                       resolve_scale(scale, d), workspace, workspace_bytes};
-    a.scale64 = resolve_scale64(scale, d);
-    a.local = 1;
-    a.left = left;
-    a.right = right;
-    rc = fa::launch_dense_bwd(a, (hipStream_t)hip_stream, &why);
-    return rc == FA_OK ? ok() : fail(rc, fn, why);
-}
-
-// Not part of the public header (tests): the plans of a local call, as fa_debug_dense_fwd_plan /
-// fa_debug_dense_bwd_plan give the dense and causal ones (those hooks keep their signatures).
-// Returns the kernel family (a fa::DenseFwdKernel / fa::DenseBwdKernel; -1: invalid arguments).
-// The window is not an argument: no plan depends on it.  Planned under the default knobs.
-// forward out[8]: local, causal bits, pad, ldk, nsplit, rows, grid, total; backward out[6]:
-// padded, N, Nk, d, dv as run, total.
-int fa_debug_local_fwd_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch,
-                            int kv_aligned16, int qo_aligned16, size_t ws_bytes, int cus, int64_t* out) {
-    if (!valid_dtype(dtype) || N < 1 || Nk < N || d < 1 || dv < 1 || batch < 1) return -1;
-    const fa::DenseFwdPlan pl = fa::dense_fwd_plan(dtype, N, Nk, d, dv, batch, fa::kMaskLocal, {fa::kFwdAuto, 0},
-                                                   kv_aligned16 != 0, qo_aligned16 != 0, ws_bytes, cus);
-    if (out) {
-        const int64_t f[8] = {pl.local, pl.causal, pl.pad, pl.ldk, pl.nsplit, pl.rows, pl.grid, (int64_t)pl.total};
-        for (int i = 0; i < 8; ++i) out[i] = f[i];
-    }
-    return pl.kernel;
-}
-int fa_debug_local_bwd_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch,
-                            int qkvdo_aligned16, size_t ws_bytes, int cus, int64_t* out) {
-    if (!valid_dtype(dtype) || N < 1 || Nk < N || d < 1 || dv < 1 || batch < 1 || d > fa::kMaxHeadDim ||
-        dv > fa::kMaxHeadDim)
-        return -1;
-    const fa::DenseBwdPlan pl = fa::dense_bwd_plan(dtype, N, Nk, d, dv, batch, fa::kMaskLocal,
-                                                   {0, fa::kBwdAuto, 3, -1}, qkvdo_aligned16 != 0, ws_bytes, cus);
-    if (out) {
-        const int64_t f[6] = {pl.padded, pl.N, pl.Nk, pl.d, pl.dv, (int64_t)pl.total};
-        for (int i = 0; i < 6; ++i) out[i] = f[i];
-    }
-    return pl.kernel;
 }
 
 int fa_dense_bwd_handoff_status(const void* workspace, size_t workspace_bytes, void* hip_stream, int* status) {

@@ -75,7 +75,7 @@ struct BwdParams {
     int causal = 0, off = 0;
     // local (fa_local_bwd; read by the LOCAL instantiations only, which also read off): query i
     // sees keys i + off - left <= j <= i + off + right, both sides clamped to [0, Nk] of the
-    // caller's extents, where Nk binds nowhere (local_clamp)
+    // caller's extents, where Nk binds nowhere (mask_ints)
     int local = 0, left = 0, right = 0;
 };
 
@@ -131,8 +131,9 @@ constexpr int kGT = 32;          // tile edge
 constexpr int kGThreads = 256;
 
 // dQ: one block per (b, 32-query tile).
-template <class T, class A, bool CAUSAL = false, bool LOCAL = false>
+template <class T, class A, DenseMask MASK = kMaskNone>
 __global__ __launch_bounds__(kGThreads) void bwd_generic_dq(BwdParams p) {
+    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal;
     extern __shared__ __attribute__((aligned(16))) char gsm_raw[];
     A* const gsm = (A*)gsm_raw;
     const int d = p.d, dv = p.dv, N = p.N, Nk = p.Nk, ld = d + 1, ldv = dv + 1;
@@ -218,8 +219,9 @@ __global__ __launch_bounds__(kGThreads) void bwd_generic_dq(BwdParams p) {
 }
 
 // dK, dV: one block per (b, 32-key tile).
-template <class T, class A, bool CAUSAL = false, bool LOCAL = false>
+template <class T, class A, DenseMask MASK = kMaskNone>
 __global__ __launch_bounds__(kGThreads) void bwd_generic_dkdv(BwdParams p) {
+    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal;
     extern __shared__ __attribute__((aligned(16))) char gsm_raw[];
     A* const gsm = (A*)gsm_raw;
     const int d = p.d, dv = p.dv, N = p.N, Nk = p.Nk, ld = d + 1, ldv = dv + 1;
@@ -335,8 +337,9 @@ __global__ __launch_bounds__(kGThreads) void bwd_generic_dkdv(BwdParams p) {
 constexpr int kF32T = 32;   // tile of the streamed side
 constexpr int kF32R = 33;   // LDS row (floats)
 
-template <int D, int DV, bool CAUSAL = false, bool LOCAL = false>
+template <int D, int DV, DenseMask MASK = kMaskNone>
 __global__ __launch_bounds__(256) void bwd_dkdv_f32(BwdParams p) {
+    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal;
     __shared__ float sQ[D * kF32R], sdO[DV * kF32R], sL[kF32T], sD[kF32T];
     const int N = p.N, Nk = p.Nk, d = p.d, dv = p.dv;
     const int nkb = (Nk + 127) / 128;
@@ -436,8 +439,9 @@ __global__ __launch_bounds__(256) void bwd_dkdv_f32(BwdParams p) {
     }
 }
 
-template <int D, int DV, bool CAUSAL = false, bool LOCAL = false>
+template <int D, int DV, DenseMask MASK = kMaskNone>
 __global__ __launch_bounds__(256) void bwd_dq_f32(BwdParams p) {
+    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal;
     __shared__ float sK[D * kF32R], sV[DV * kF32R];
     const int N = p.N, Nk = p.Nk, d = p.d, dv = p.dv;
     const int nqb = (N + 127) / 128;
@@ -519,24 +523,22 @@ __global__ __launch_bounds__(256) void bwd_dq_f32(BwdParams p) {
 }
 
 template <int D, int DV>
-static hipError_t launch_f32_dd(const BwdParams& p, hipStream_t s) {
+static hipError_t launch_f32_dd(const BwdParams& p, DenseMask mask, hipStream_t s) {
     const int64_t nq = ((int64_t)p.N + 127) / 128 * p.batch, nk = ((int64_t)p.Nk + 127) / 128 * p.batch;
-    void (*dq)(BwdParams) = p.local ? bwd_dq_f32<D, DV, false, true> : p.causal ? bwd_dq_f32<D, DV, true> : bwd_dq_f32<D, DV>;
-    void (*dkdv)(BwdParams) = p.local    ? bwd_dkdv_f32<D, DV, false, true>
-                              : p.causal ? bwd_dkdv_f32<D, DV, true>
-                                         : bwd_dkdv_f32<D, DV>;
-    hipLaunchKernelGGL(dq, dim3((unsigned)nq), dim3(256), 0, s, p);
-    hipLaunchKernelGGL(dkdv, dim3((unsigned)nk), dim3(256), 0, s, p);
+    by_mask(mask, [&](auto M) {
+        hipLaunchKernelGGL((bwd_dq_f32<D, DV, decltype(M)::value>), dim3((unsigned)nq), dim3(256), 0, s, p);
+        hipLaunchKernelGGL((bwd_dkdv_f32<D, DV, decltype(M)::value>), dim3((unsigned)nk), dim3(256), 0, s, p);
+    });
     return hipGetLastError();
 }
 // (five class pairs, not nine: any d or dv above 64 runs the 128 x 128 kernels)
-static hipError_t launch_f32_mfma(const BwdParams& p, hipStream_t s) {
-    if (p.d > 64 || p.dv > 64) return launch_f32_dd<128, 128>(p, s);
+static hipError_t launch_f32_mfma(const BwdParams& p, DenseMask mask, hipStream_t s) {
+    if (p.d > 64 || p.dv > 64) return launch_f32_dd<128, 128>(p, mask, s);
     const int Dc = p.d <= 32 ? 32 : 64, DVc = p.dv <= 32 ? 32 : 64;
-    if (Dc == 32 && DVc == 32) return launch_f32_dd<32, 32>(p, s);
-    if (Dc == 32) return launch_f32_dd<32, 64>(p, s);
-    if (DVc == 32) return launch_f32_dd<64, 32>(p, s);
-    return launch_f32_dd<64, 64>(p, s);
+    if (Dc == 32 && DVc == 32) return launch_f32_dd<32, 32>(p, mask, s);
+    if (Dc == 32) return launch_f32_dd<32, 64>(p, mask, s);
+    if (DVc == 32) return launch_f32_dd<64, 32>(p, mask, s);
+    return launch_f32_dd<64, 64>(p, mask, s);
 }
 
 // --------------------------------------------------------------------------
@@ -620,8 +622,9 @@ __device__ void fused_combine(const BwdParams& p, int b, int qb) {
 // LOCAL (fa_local_bwd, likewise never after bwd_fused): the key tiles run from the block's first
 // query's left edge to its last query's right edge, a wave skips the tiles wholly outside
 // its own band, and S is selected to -inf on the tiles that straddle either of its diagonals.
-template <class T, int D, int DV, bool CAUSAL = false, bool LOCAL = false>
+template <class T, int D, int DV, DenseMask MASK = kMaskNone>
 __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
+    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal;
     typedef typename Frag8<T>::type F8;
     constexpr int KB = D * 128, VB = DV * 128, STAGE = KB + VB;
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
@@ -777,8 +780,9 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
 // whole pipeline (row constants, DMA, barriers) is then skipped, block-uniformly, and the
 // zero accumulators are stored.  A wave skips the tiles outside its own keys' range and
 // selects on the tiles that straddle either diagonal.
-template <class T, int D, int DV, bool CAUSAL = false, bool LOCAL = false>
+template <class T, int D, int DV, DenseMask MASK = kMaskNone>
 __global__ __launch_bounds__(256, 2) void bwd_dkdv_fast(BwdParams p) {
+    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal;
     typedef typename Frag8<T>::type F8;
     constexpr int QB = D * 128, OB = DV * 128, STAGE = QB + OB + 512;
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
@@ -1756,7 +1760,7 @@ static hipError_t unpad_launch(const void* src, void* dst, int64_t N, int64_t C,
 
 // kDenseBwdTwoPass / kDenseBwdSinglePass at (d, dv) = (D, DV)
 template <class T, int D, int DV>
-static hipError_t launch_fast_dd(const DenseBwdPlan& pl, BwdParams p, hipStream_t s) {
+static hipError_t launch_fast_dd(const DenseBwdPlan& pl, BwdParams p, DenseMask mask, hipStream_t s) {
     // a pass of 128-row blocks over `rows`
     auto pass = [&](void (*kernel)(BwdParams), int rows) {
         p.nblk = (rows + 127) / 128;
@@ -1773,47 +1777,44 @@ static hipError_t launch_fast_dd(const DenseBwdPlan& pl, BwdParams p, hipStream_
         p.cguard = p.hdr + 3;
         p.fin = p.flags + ff.fin;
     }
-    // (causal: always the two passes: no atomics, no hand-off)
-    // (local: likewise)
-    pass(p.local ? bwd_dq_fast<T, D, DV, false, true> : p.causal ? bwd_dq_fast<T, D, DV, true> : bwd_dq_fast<T, D, DV>, p.N);
-    if (!single)
-        pass(p.local    ? bwd_dkdv_fast<T, D, DV, false, true>
-             : p.causal ? bwd_dkdv_fast<T, D, DV, true>
-                        : bwd_dkdv_fast<T, D, DV>,
-             p.Nk);
+    // (a masked backward is always the two passes: no atomics, no hand-off)
+    by_mask(mask, [&](auto M) {
+        pass(bwd_dq_fast<T, D, DV, decltype(M)::value>, p.N);
+        if (!single) pass(bwd_dkdv_fast<T, D, DV, decltype(M)::value>, p.Nk);
+    });
     return hipGetLastError();
 }
 template <class T>
-static hipError_t launch_fast(const DenseBwdPlan& pl, const BwdParams& p, hipStream_t s) {
+static hipError_t launch_fast(const DenseBwdPlan& pl, const BwdParams& p, DenseMask mask, hipStream_t s) {
     hipError_t e = hipErrorInvalidValue;
     by_dim_class(p.d, [&](auto D) {
-        by_dim_class(p.dv, [&](auto DV) { e = launch_fast_dd<T, decltype(D)::value, decltype(DV)::value>(pl, p, s); });
+        by_dim_class(p.dv, [&](auto DV) { e = launch_fast_dd<T, decltype(D)::value, decltype(DV)::value>(pl, p, mask, s); });
     });
     return e;
 }
 
 template <class T, class A = float>
-static hipError_t launch_generic(const BwdParams& p, hipStream_t s) {
+static hipError_t launch_generic(const BwdParams& p, DenseMask mask, hipStream_t s) {
     const int64_t nq = ((int64_t)p.N + kGT - 1) / kGT * p.batch;
     const int64_t nk = ((int64_t)p.Nk + kGT - 1) / kGT * p.batch;
     const size_t rows = kGT * (2 * (p.d + 1) + 2 * (p.dv + 1));
     const size_t sm_dq = sizeof(A) * (rows + kGT * (kGT + 1));
     const size_t sm_kv = sizeof(A) * (rows + 2 * kGT * (kGT + 1));
-    void (*dq)(BwdParams) = p.local ? bwd_generic_dq<T, A, false, true> : p.causal ? bwd_generic_dq<T, A, true> : bwd_generic_dq<T, A>;
-    void (*dkdv)(BwdParams) = p.local    ? bwd_generic_dkdv<T, A, false, true>
-                              : p.causal ? bwd_generic_dkdv<T, A, true>
-                                         : bwd_generic_dkdv<T, A>;
-    // > 64 KiB of dynamic LDS at d = dv = 128 (gfx950 has 160 KiB per CU)
-    (void)hipFuncSetAttribute((const void*)dq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_dq);
-    (void)hipFuncSetAttribute((const void*)dkdv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_kv);
-    hipLaunchKernelGGL(dq, dim3((unsigned)nq), dim3(kGThreads), sm_dq, s, p);
-    hipLaunchKernelGGL(dkdv, dim3((unsigned)nk), dim3(kGThreads), sm_kv, s, p);
+    by_mask(mask, [&](auto M) {
+        void (*dq)(BwdParams) = bwd_generic_dq<T, A, decltype(M)::value>;
+        void (*dkdv)(BwdParams) = bwd_generic_dkdv<T, A, decltype(M)::value>;
+        // > 64 KiB of dynamic LDS at d = dv = 128 (gfx950 has 160 KiB per CU)
+        (void)hipFuncSetAttribute((const void*)dq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_dq);
+        (void)hipFuncSetAttribute((const void*)dkdv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_kv);
+        hipLaunchKernelGGL(dq, dim3((unsigned)nq), dim3(kGThreads), sm_dq, s, p);
+        hipLaunchKernelGGL(dkdv, dim3((unsigned)nk), dim3(kGThreads), sm_kv, s, p);
+    });
     return hipGetLastError();
 }
 
 // the pre-pass, then the plan's kernel
 template <class T>
-static hipError_t launch_typed(const DenseBwdPlan& pl, const BwdParams& p, hipStream_t s) {
+static hipError_t launch_typed(const DenseBwdPlan& pl, const BwdParams& p, DenseMask mask, hipStream_t s) {
     const int64_t total = (int64_t)p.N * p.batch;
     bool vec = false;
     if constexpr (sizeof(T) == 2) {
@@ -1824,27 +1825,22 @@ static hipError_t launch_typed(const DenseBwdPlan& pl, const BwdParams& p, hipSt
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if constexpr (std::is_same<T, float>::value) {
-        if (pl.kernel == kDenseBwdF32Mfma) return launch_f32_mfma(p, s);
+        if (pl.kernel == kDenseBwdF32Mfma) return launch_f32_mfma(p, mask, s);
     } else {
-        if (pl.kernel == kDenseBwdTwoPass || pl.kernel == kDenseBwdSinglePass) return launch_fast<T>(pl, p, s);
+        if (pl.kernel == kDenseBwdTwoPass || pl.kernel == kDenseBwdSinglePass) return launch_fast<T>(pl, p, mask, s);
     }
-    return launch_generic<T>(p, s);
+    return launch_generic<T>(p, mask, s);
 }
 
 static DenseBwdKnobs bwd_knobs() { return {g_bwd_force_generic, g_bwd_mode, g_bwd_hoff, g_bwd_xcd}; }
 
 // The shape's own needs under the thread's knobs on the current device: aligned tensors, room
 // for everything (the queries have no pointers).
-size_t dense_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    return dense_bwd_plan(dtype, N, Nk, d, dv, batch, kMaskNone, bwd_knobs(), true, SIZE_MAX, device_cus(nullptr)).total;
-}
-// fa_causal_bwd: header, row statistics, padded slabs; never the single pass's part (and so no device query)
-size_t causal_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    return dense_bwd_plan(dtype, N, Nk, d, dv, batch, kMaskCausal, bwd_knobs(), true, SIZE_MAX, 0).total;
-}
-// fa_local_bwd: the same, whatever the window
-size_t local_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    return dense_bwd_plan(dtype, N, Nk, d, dv, batch, kMaskLocal, bwd_knobs(), true, SIZE_MAX, 0).total;
+// A masked backward: header, row statistics, padded slabs; never the single pass's part, and so
+// no device query.
+size_t dense_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, DenseMask mask) {
+    const int cus = mask == kMaskNone ? device_cus(nullptr) : 0;
+    return dense_bwd_plan(dtype, N, Nk, d, dv, batch, mask, bwd_knobs(), true, SIZE_MAX, cus).total;
 }
 
 // Single-pass state in the workspace: per-slice counters (zeroed here), then the running dQ
@@ -1900,14 +1896,7 @@ int launch_dense_bwd(const DenseBwdArgs& a, hipStream_t s, const char** why) {
         *why = "head dimension exceeds the compiled maximum (128)";
         return FA_ERR_UNSUPPORTED;
     }
-    if (a.causal && a.Nk < a.N) {
-        *why = "causal attention needs Nk >= N (a query would see no key)";
-        return FA_ERR_UNSUPPORTED;
-    }
-    if (a.local && a.Nk < a.N) {
-        *why = "local attention needs Nk >= N (a query would see no key)";
-        return FA_ERR_UNSUPPORTED;
-    }
+    if (mask_lacks_keys(a.mask, a.N, a.Nk, why)) return FA_ERR_UNSUPPORTED;
     if (a.N * a.d > INT32_MAX || a.Nk * a.d > INT32_MAX || a.N * a.dv > INT32_MAX ||
         a.Nk * a.dv > INT32_MAX || a.N * a.batch > INT32_MAX / 2 || a.Nk * a.batch > INT32_MAX / 2) {
         *why = "extent exceeds 2^31 elements";
@@ -1916,25 +1905,20 @@ int launch_dense_bwd(const DenseBwdArgs& a, hipStream_t s, const char** why) {
     const DenseBwdKnobs kn = bwd_knobs();
     char* const w = al256(a.workspace);
     const size_t slack = (size_t)(w - (char*)a.workspace);
-    const DenseBwdPlan pl = dense_bwd_plan(a.dtype, a.N, a.Nk, a.d, a.dv, a.batch, dense_mask(a.causal, a.local), kn,
+    const DenseBwdPlan pl = dense_bwd_plan(a.dtype, a.N, a.Nk, a.d, a.dv, a.batch, a.mask, kn,
                                            aligned16(a.Q) && aligned16(a.K) && aligned16(a.V) && aligned16(a.dO),
                                            a.workspace_bytes > slack ? a.workspace_bytes - slack : 0, device_cus(s));
     // causal, local and Float64 totals depend on the shape alone: the whole of it must be there.
     // (A padded call checks its slabs below; the single pass's part is optional.)
-    if ((a.causal || a.local || a.dtype == FA_DTYPE_F64) && a.workspace_bytes < pl.total) {
-        *why = a.local    ? "workspace smaller than fa_local_bwd_workspace()"
-               : a.causal ? "workspace smaller than fa_causal_bwd_workspace()"
-                          : "workspace smaller than fa_dense_bwd_workspace()";
+    if ((a.mask != kMaskNone || a.dtype == FA_DTYPE_F64) && a.workspace_bytes < pl.total) {
+        *why = a.mask == kMaskLocal    ? "workspace smaller than fa_local_bwd_workspace()"
+               : a.mask == kMaskCausal ? "workspace smaller than fa_causal_bwd_workspace()"
+                                       : "workspace smaller than fa_dense_bwd_workspace()";
         return FA_ERR_WORKSPACE;
     }
     BwdParams p;
-    p.causal = a.causal && !a.local ? 1 : 0;
-    p.off = a.causal || a.local ? (int)(a.Nk - a.N) : 0;   // from the caller's extents, also on the padded path
-    if (a.local) {   // the window too
-        p.local = 1;
-        p.left = local_clamp(a.left, a.Nk);
-        p.right = local_clamp(a.right, a.Nk);
-    }
+    const MaskInts mi = mask_ints(a.mask, a.left, a.right, a.N, a.Nk);   // from the caller's extents, also on the padded path
+    p.causal = mi.causal; p.off = mi.off; p.local = mi.local; p.left = mi.left; p.right = mi.right;
     p.Q = a.Q; p.K = a.K; p.V = a.V; p.O = a.O; p.dO = a.dO; p.l = a.l; p.m = a.m;
     p.dQ = a.dQ; p.dK = a.dK; p.dV = a.dV;
     p.hdr = (unsigned*)(w + pl.off_hdr);
@@ -1960,7 +1944,7 @@ int launch_dense_bwd(const DenseBwdArgs& a, hipStream_t s, const char** why) {
         p.scale64 = a.scale64 > 0.0 ? a.scale64 : (double)a.scale;
         const int rc = launch_f64_bwd_stats(a, (double*)p.nD, (double*)p.nlse, s, why);
         if (rc != FA_OK) return rc;
-        if ((e = launch_generic<double, double>(p, s)) != hipSuccess) {   // (causal: its CAUSAL instantiations)
+        if ((e = launch_generic<double, double>(p, a.mask, s)) != hipSuccess) {
             *why = hipGetErrorString(e);
             return FA_ERR_HIP;
         }
@@ -2000,15 +1984,15 @@ int launch_dense_bwd(const DenseBwdArgs& a, hipStream_t s, const char** why) {
         p.l = (const float*)slab(kSlabL); p.m = (const float*)slab(kSlabM);
         p.dQ = slab(kSlabDQ); p.dK = slab(kSlabDK); p.dV = slab(kSlabDV);
         p.N = (int)pl.N; p.Nk = (int)pl.Nk; p.d = (int)pl.d; p.dv = (int)pl.dv;
-        e = half ? launch_typed<f16>(pl, p, s) : launch_typed<bf16>(pl, p, s);
+        e = half ? launch_typed<f16>(pl, p, a.mask, s) : launch_typed<bf16>(pl, p, a.mask, s);
         if (e == hipSuccess && (e = unpad(kSlabDQ, a.dQ, a.N, a.d, pl.N, pl.d)) == hipSuccess &&
             (e = unpad(kSlabDK, a.dK, a.Nk, a.d, pl.Nk, pl.d)) == hipSuccess)
             e = unpad(kSlabDV, a.dV, a.Nk, a.dv, pl.Nk, pl.dv);
     } else {
         switch (a.dtype) {
-            case FA_DTYPE_BF16: e = launch_typed<bf16>(pl, p, s); break;
-            case FA_DTYPE_F16: e = launch_typed<f16>(pl, p, s); break;
-            case FA_DTYPE_F32: e = launch_typed<float>(pl, p, s); break;
+            case FA_DTYPE_BF16: e = launch_typed<bf16>(pl, p, a.mask, s); break;
+            case FA_DTYPE_F16: e = launch_typed<f16>(pl, p, a.mask, s); break;
+            case FA_DTYPE_F32: e = launch_typed<float>(pl, p, a.mask, s); break;
             default: *why = "unknown dtype"; return FA_ERR_INVALID_ARG;
         }
     }

@@ -6,6 +6,10 @@
 // launchers ask once and switch on the answer, the workspace entry points return the same
 // plan's total, fa_debug_dense_fwd_plan / fa_debug_dense_bwd_plan (api.cpp) return it for
 // tests, and tests/test_dense_plan_host.py pins the choice.
+//
+// The mask is one DenseMask (fa_internal.h) from the entry points on: both plans take it, the
+// forward plan hands it on (DenseFwdPlan::mask) and the launchers instantiate the plan's
+// kernel with it as the kernel's MASK template argument (by_mask).
 #pragma once
 
 #include <algorithm>
@@ -32,9 +36,8 @@ enum DenseFwdVariant : int {
     kFwdP4 = 30,       // the one-wave-per-SIMD persistent kernel wherever its shape rules allow
 };
 
-// The causal twins (causal_fwd_*, the CAUSAL instantiations of the generic kernels) are the
-// same enumerator with DenseFwdPlan::causal != 0, the local ones (local_fwd_*, the LOCAL
-// instantiations) with DenseFwdPlan::local.
+// A causal or local launch is the same enumerator with DenseFwdPlan::mask: the kernel named
+// here, instantiated with MASK = kMaskCausal / kMaskLocal.
 enum DenseFwdKernel : int {
     kDenseFwdNone = -1,        // a head dimension above kMaxHeadDim: the launcher refuses
     kDenseFwdGeneric = 0,      // dense_fwd_generic (SIMT, any shape and alignment)
@@ -59,7 +62,7 @@ struct DenseFwdPlan {
     // FwdParams::causal: 0 dense; bit 0 causal, bit 1 a slab's heaviest query block first,
     // bit 2 block-major inside an XCD's share of the grid (dense_fwd_tiled)
     int causal = 0;
-    bool local = false;    // fa_local_fwd: the LOCAL instantiations (never with causal bits, never split, never p4)
+    DenseMask mask = kMaskNone;   // the kernel's MASK (causal bits only under kMaskCausal; a masked launch never splits, never p4)
     bool kv_vec = false;   // FwdParams::fast: K / V rows take 16-B loads (after padding, if any)
     bool wide = false;     // FwdParams::wide: N % 8 == 0, Q and O 16-B aligned
     bool pad = false;      // K / V are first copied to zero-padded slabs of row stride ldk
@@ -118,7 +121,7 @@ inline DenseFwdPlan dense_fwd_plan(int dtype, int64_t N, int64_t Nk, int64_t d, 
                                    size_t ws_bytes, int cus) {
     DenseFwdPlan pl;
     const bool causal = mask == kMaskCausal;
-    pl.local = mask == kMaskLocal;
+    pl.mask = mask;
     if (dtype == FA_DTYPE_F64) {
         pl.kernel = kDenseFwdF64;
         return pl;

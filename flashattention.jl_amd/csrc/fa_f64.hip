@@ -38,7 +38,7 @@ struct F64Params {
     int N, Nk, d, dv, nqb;
     double scale;
     int causal = 0, off = 0;   // CAUSAL instantiations: query i sees keys j <= i + off (off = Nk - N)
-    // LOCAL instantiations: keys i + off - left <= j <= i + off + right, each side in [0, Nk] (local_clamp)
+    // LOCAL instantiations: keys i + off - left <= j <= i + off + right, each side in [0, Nk] (mask_ints)
     int local = 0, left = 0, right = 0;
 };
 
@@ -55,8 +55,9 @@ static size_t f64_lds_bytes(int d, int dv, bool stats, int QB) {
 
 // QB queries per workgroup, NG = 256/QB thread groups per query: group g scores
 // keys KPG·g .. KPG·g + KPG−1 of each tile and owns output channels g, g + NG, ….
-template <bool STATS, int QB, bool CAUSAL = false, bool LOCAL = false>
+template <bool STATS, int QB, DenseMask MASK = kMaskNone>
 __global__ __launch_bounds__(kTh64) void dense_fwd_f64(F64Params p) {
+    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal;
     constexpr int NG = kTh64 / QB, KPG = kKB64 / NG, OPER = kMaxHeadDim / NG;
     static_assert(KPG >= 1 && QB * NG == kTh64, "geometry");
     extern __shared__ __attribute__((aligned(16))) double sm64[];
@@ -200,20 +201,12 @@ __global__ __launch_bounds__(256) void bwd_rowdot_f64(const double* __restrict__
     nD[idx] = -acc;
 }
 
-static bool f64_fits(int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, const char** why, int causal = 0,
-                     int local = 0) {
+static bool f64_fits(int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, const char** why, DenseMask mask) {
     if (d > kMaxHeadDim || dv > kMaxHeadDim) {
         *why = "head dimension exceeds the compiled maximum (128)";
         return false;
     }
-    if (causal && Nk < N) {
-        *why = "causal attention needs Nk >= N (a query would see no key)";
-        return false;
-    }
-    if (local && Nk < N) {
-        *why = "local attention needs Nk >= N (a query would see no key)";
-        return false;
-    }
+    if (mask_lacks_keys(mask, N, Nk, why)) return false;
     if (N > INT32_MAX / 2 || Nk > INT32_MAX / 2 || (N + kQB64 - 1) / kQB64 * batch > INT32_MAX) {
         *why = "extent exceeds the 32-bit grid";
         return false;
@@ -222,50 +215,40 @@ static bool f64_fits(int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch
 }
 
 template <bool STATS, int QB>
-static hipError_t launch_f64_qb(F64Params p, int64_t batch, hipStream_t s) {
+static hipError_t launch_f64_qb(F64Params p, int64_t batch, DenseMask mask, hipStream_t s) {
     p.nqb = (p.N + QB - 1) / QB;
     const size_t lds = f64_lds_bytes(p.d, p.dv, STATS, QB);
-    if (p.local) {
-        (void)hipFuncSetAttribute((const void*)dense_fwd_f64<STATS, QB, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds);
-        hipLaunchKernelGGL((dense_fwd_f64<STATS, QB, false, true>), dim3((unsigned)(p.nqb * batch)), dim3(kTh64), lds, s, p);
-        return hipGetLastError();
-    }
-    if (p.causal) {
-        (void)hipFuncSetAttribute((const void*)dense_fwd_f64<STATS, QB, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds);
-        hipLaunchKernelGGL((dense_fwd_f64<STATS, QB, true>), dim3((unsigned)(p.nqb * batch)), dim3(kTh64), lds, s, p);
-        return hipGetLastError();
-    }
-    (void)hipFuncSetAttribute((const void*)dense_fwd_f64<STATS, QB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-    hipLaunchKernelGGL((dense_fwd_f64<STATS, QB>), dim3((unsigned)(p.nqb * batch)), dim3(kTh64), lds, s, p);
+    by_mask(mask, [&](auto M) {
+        void (*kernel)(F64Params) = dense_fwd_f64<STATS, QB, decltype(M)::value>;
+        (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(p.nqb * batch)), dim3(kTh64), lds, s, p);
+    });
     return hipGetLastError();
 }
 // 64 queries per workgroup when that fills the chip, else 16 (4x the workgroups:
 // the reference's own Float64 cases are single slabs of 256-16384 tokens)
 template <bool STATS>
-static hipError_t launch_f64_kernel(const F64Params& p, int64_t batch, hipStream_t s) {
-    if ((int64_t)((p.N + kQB64 - 1) / kQB64) * batch >= 256) return launch_f64_qb<STATS, kQB64>(p, batch, s);
-    return launch_f64_qb<STATS, 16>(p, batch, s);
+static hipError_t launch_f64_kernel(const F64Params& p, int64_t batch, DenseMask mask, hipStream_t s) {
+    if ((int64_t)((p.N + kQB64 - 1) / kQB64) * batch >= 256) return launch_f64_qb<STATS, kQB64>(p, batch, mask, s);
+    return launch_f64_qb<STATS, 16>(p, batch, mask, s);
+}
+
+// the mask's five ints, from the caller's extents and window
+static void set_mask(F64Params& p, DenseMask mask, int64_t left, int64_t right, int64_t N, int64_t Nk) {
+    const MaskInts mi = mask_ints(mask, left, right, N, Nk);
+    p.causal = mi.causal; p.off = mi.off; p.local = mi.local; p.left = mi.left; p.right = mi.right;
 }
 
 int launch_dense_fwd_f64(const DenseArgs& a, hipStream_t s, const char** why) {
-    if (!f64_fits(a.N, a.Nk, a.d, a.dv, a.batch, why, a.causal, a.local)) return FA_ERR_UNSUPPORTED;
+    if (!f64_fits(a.N, a.Nk, a.d, a.dv, a.batch, why, a.mask)) return FA_ERR_UNSUPPORTED;
     F64Params p;
     p.Q = (const double*)a.Q; p.K = (const double*)a.K; p.V = (const double*)a.V; p.O = (double*)a.O;
     p.l = a.l; p.m = a.m; p.nlse = nullptr;
     p.N = (int)a.N; p.Nk = (int)a.Nk; p.d = (int)a.d; p.dv = (int)a.dv;
     p.nqb = (int)((a.N + kQB64 - 1) / kQB64);
     p.scale = a.scale64 > 0.0 ? a.scale64 : (double)a.scale;
-    p.causal = a.causal && !a.local ? 1 : 0;
-    p.off = a.causal || a.local ? (int)(a.Nk - a.N) : 0;
-    if (a.local) {
-        p.local = 1;
-        p.left = local_clamp(a.left, a.Nk);
-        p.right = local_clamp(a.right, a.Nk);
-    }
-    const hipError_t e = launch_f64_kernel<false>(p, a.batch, s);
+    set_mask(p, a.mask, a.left, a.right, a.N, a.Nk);
+    const hipError_t e = launch_f64_kernel<false>(p, a.batch, a.mask, s);
     if (e != hipSuccess) {
         *why = hipGetErrorString(e);
         return FA_ERR_HIP;
@@ -274,21 +257,15 @@ int launch_dense_fwd_f64(const DenseArgs& a, hipStream_t s, const char** why) {
 }
 
 int launch_f64_bwd_stats(const DenseBwdArgs& a, double* nD, double* nlse, hipStream_t s, const char** why) {
-    if (!f64_fits(a.N, a.Nk, a.d, a.dv, a.batch, why, a.causal, a.local)) return FA_ERR_UNSUPPORTED;
+    if (!f64_fits(a.N, a.Nk, a.d, a.dv, a.batch, why, a.mask)) return FA_ERR_UNSUPPORTED;
     F64Params p;
     p.Q = (const double*)a.Q; p.K = (const double*)a.K; p.V = nullptr; p.O = nullptr;
     p.l = nullptr; p.m = nullptr; p.nlse = nlse;
     p.N = (int)a.N; p.Nk = (int)a.Nk; p.d = (int)a.d; p.dv = (int)a.dv;
     p.nqb = (int)((a.N + kQB64 - 1) / kQB64);
     p.scale = a.scale64 > 0.0 ? a.scale64 : (double)a.scale;
-    p.causal = a.causal && !a.local ? 1 : 0;
-    p.off = a.causal || a.local ? (int)(a.Nk - a.N) : 0;
-    if (a.local) {
-        p.local = 1;
-        p.left = local_clamp(a.left, a.Nk);
-        p.right = local_clamp(a.right, a.Nk);
-    }
-    hipError_t e = launch_f64_kernel<true>(p, a.batch, s);
+    set_mask(p, a.mask, a.left, a.right, a.N, a.Nk);
+    hipError_t e = launch_f64_kernel<true>(p, a.batch, a.mask, s);
     if (e == hipSuccess) {
         const int64_t total = a.N * a.batch;
         hipLaunchKernelGGL(bwd_rowdot_f64, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,

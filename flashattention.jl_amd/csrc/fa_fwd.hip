@@ -143,8 +143,9 @@ __device__ __forceinline__ int local_ntiles(int nt, int q_last, int N, int off, 
 // --------------------------------------------------------------------------
 // bf16 / fp16 forward (v_mfma_f32_32x32x16_{bf16,f16})
 // --------------------------------------------------------------------------
-template <class T, int D, int DV, bool CAUSAL = false, bool LOCAL = false>
+template <class T, int D, int DV, DenseMask MASK = kMaskNone>
 __global__ __launch_bounds__(kThreads) void dense_fwd_generic(FwdParams p) {
+    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal;
     typedef typename Frag8<T>::type F8;
     typedef typename Frag8<T>::half F4;
     constexpr int KROW = kBN * 2;       // K image: [D][64 keys], 128-B rows, 32-B chunk XOR swizzle
@@ -369,8 +370,9 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic(FwdParams p) {
 // --------------------------------------------------------------------------
 // fp32 forward (exact f32 MFMA v_mfma_f32_32x32x2_f32)
 // --------------------------------------------------------------------------
-template <int D, int DV, bool CAUSAL = false, bool LOCAL = false>
+template <int D, int DV, DenseMask MASK = kMaskNone>
 __global__ __launch_bounds__(kThreads) void dense_fwd_generic_f32(FwdParams p) {
+    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal;
     constexpr int KROWF = kBN;       // K image [D][64] floats
     constexpr int VROWF = kBN + 1;   // V image [DV][65] floats (pad → conflict-free column reads)
     constexpr int KCH = D * 16 / kThreads;
@@ -598,11 +600,11 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic_f32(FwdParams p) {
 // ragged mask can meet in one tile).  A row whose window begins after the wave's first tile
 // keeps m_used = -inf there: the rescale is row-local as for CAUSAL, with alpha = 1 for a row
 // that does not move, and the exponent's offset is 0 while m_used = -inf (P = 0).
-template <class T, int D, int DV, int NW, int BN, int NQB, bool SPLIT = false, bool WIDE = false, bool CAUSAL = false,
-          bool LOCAL = false>
+template <class T, int D, int DV, int NW, int BN, int NQB, bool SPLIT = false, bool WIDE = false, DenseMask MASK = kMaskNone>
 __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
+    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal;
     static_assert(!(CAUSAL && SPLIT), "causal launches never split the keys");
-    static_assert(!(LOCAL && (SPLIT || CAUSAL)), "local launches never split the keys; LOCAL is a mode of its own");
+    static_assert(!(LOCAL && SPLIT), "local launches never split the keys");
     typedef typename Frag8<T>::type F8;
     typedef typename Frag8<T>::half F4;
     constexpr int NTH = 64 * NW;
@@ -1092,46 +1094,23 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
     }
 }
 
-template <class T, int D, int DV>
-__global__ __launch_bounds__(512, 1) void dense_fwd_w8b64(FwdParams p) { dense_fwd_tiled<T, D, DV, 8, 64, 1>(p); }
-template <class T, int D, int DV>
-__global__ __launch_bounds__(512, 1) void dense_fwd_w8q2(FwdParams p) { dense_fwd_tiled<T, D, DV, 8, 64, 2>(p); }
-// the default geometries with LDS-staged Q / O (N % 8 == 0, Q and O 16-B aligned)
-template <class T, int D, int DV>
+// the four default geometries under a mask (a masked launch never splits, never runs fa_fwd_p4)
+template <class T, int D, int DV, DenseMask MASK = kMaskNone>
+__global__ __launch_bounds__(512, 1) void dense_fwd_w8b64(FwdParams p) { dense_fwd_tiled<T, D, DV, 8, 64, 1, false, false, MASK>(p); }
+template <class T, int D, int DV, DenseMask MASK = kMaskNone>
+__global__ __launch_bounds__(512, 1) void dense_fwd_w8q2(FwdParams p) { dense_fwd_tiled<T, D, DV, 8, 64, 2, false, false, MASK>(p); }
+// ... with LDS-staged Q / O (N % 8 == 0, Q and O 16-B aligned)
+template <class T, int D, int DV, DenseMask MASK = kMaskNone>
 __global__ __launch_bounds__(512, 1) void dense_fwd_w8q2_wide(FwdParams p) {
-    dense_fwd_tiled<T, D, DV, 8, 64, 2, false, (D <= 64 && DV <= 64)>(p);   // the launcher picks it only there
+    dense_fwd_tiled<T, D, DV, 8, 64, 2, false, (D <= 64 && DV <= 64), MASK>(p);   // the launcher picks it only there
 }
-template <class T, int D, int DV>
-__global__ __launch_bounds__(512, 1) void dense_fwd_w8b64_wide(FwdParams p) { dense_fwd_tiled<T, D, DV, 8, 64, 1, false, true>(p); }
-// split-KV instantiations of the two default geometries (small grids)
+template <class T, int D, int DV, DenseMask MASK = kMaskNone>
+__global__ __launch_bounds__(512, 1) void dense_fwd_w8b64_wide(FwdParams p) { dense_fwd_tiled<T, D, DV, 8, 64, 1, false, true, MASK>(p); }
+// split-KV instantiations of the two default geometries (small grids; dense only)
 template <class T, int D, int DV>
 __global__ __launch_bounds__(512, 1) void dense_fwd_w8q2_split(FwdParams p) { dense_fwd_tiled<T, D, DV, 8, 64, 2, true>(p); }
 template <class T, int D, int DV>
 __global__ __launch_bounds__(512, 1) void dense_fwd_w8b64_split(FwdParams p) { dense_fwd_tiled<T, D, DV, 8, 64, 1, true>(p); }
-
-// causal instantiations of the four default geometries (fa_causal_fwd; no split-KV, no fa_fwd_p4)
-template <class T, int D, int DV>
-__global__ __launch_bounds__(512, 1) void causal_fwd_w8b64(FwdParams p) { dense_fwd_tiled<T, D, DV, 8, 64, 1, false, false, true>(p); }
-template <class T, int D, int DV>
-__global__ __launch_bounds__(512, 1) void causal_fwd_w8q2(FwdParams p) { dense_fwd_tiled<T, D, DV, 8, 64, 2, false, false, true>(p); }
-template <class T, int D, int DV>
-__global__ __launch_bounds__(512, 1) void causal_fwd_w8q2_wide(FwdParams p) {
-    dense_fwd_tiled<T, D, DV, 8, 64, 2, false, (D <= 64 && DV <= 64), true>(p);   // the launcher picks it only there
-}
-template <class T, int D, int DV>
-__global__ __launch_bounds__(512, 1) void causal_fwd_w8b64_wide(FwdParams p) { dense_fwd_tiled<T, D, DV, 8, 64, 1, false, true, true>(p); }
-
-// local instantiations of the four default geometries (fa_local_fwd; no split-KV, no fa_fwd_p4)
-template <class T, int D, int DV>
-__global__ __launch_bounds__(512, 1) void local_fwd_w8b64(FwdParams p) { dense_fwd_tiled<T, D, DV, 8, 64, 1, false, false, false, true>(p); }
-template <class T, int D, int DV>
-__global__ __launch_bounds__(512, 1) void local_fwd_w8q2(FwdParams p) { dense_fwd_tiled<T, D, DV, 8, 64, 2, false, false, false, true>(p); }
-template <class T, int D, int DV>
-__global__ __launch_bounds__(512, 1) void local_fwd_w8q2_wide(FwdParams p) {
-    dense_fwd_tiled<T, D, DV, 8, 64, 2, false, (D <= 64 && DV <= 64), false, true>(p);   // the launcher picks it only there
-}
-template <class T, int D, int DV>
-__global__ __launch_bounds__(512, 1) void local_fwd_w8b64_wide(FwdParams p) { dense_fwd_tiled<T, D, DV, 8, 64, 1, false, true, false, true>(p); }
 
 // Split-KV combine: O = Σ_s o_s·2^(c(m_s − m)) / Σ_s l_s·2^(c(m_s − m)), m = max_s m_s
 // (fixed split order: deterministic).  One thread per output element.
@@ -1180,64 +1159,56 @@ static_assert(kBM == kFwdGenericRows && kThreads == kFwdGenericThreads && kBN ==
 
 hipError_t launch_dense_fwd_p4(const FwdParams& p, int Dc, int dtype, dim3 grid, hipStream_t s);
 
-// The bf16 / fp16 kernel of a plan at head-dim classes (Dc, DVc).  Every kernel is
-// instantiated for the nine class pairs, the d = 128 forms of w8q2 included (a forced
-// kFwdW8Q2 reaches them), except the causal two-query-block kernels: d, dv <= 64 only (they
-// spill above, and the plan picks them only there); the local ones likewise.
+// The bf16 / fp16 kernel of a plan at head-dim classes (Dc, DVc) under the plan's mask.  Every
+// kernel is instantiated for the nine class pairs, the d = 128 forms of w8q2 included (a forced
+// kFwdW8Q2 reaches them), except the masked two-query-block kernels: d, dv <= 64 only (they
+// spill above, and the plan picks them only there).
 template <class T>
 static hipError_t launch_16bit(const DenseFwdPlan& pl, const FwdParams& p, int Dc, int DVc, hipStream_t s) {
     const dim3 grid((unsigned)pl.grid), blk(pl.block);
-    const bool causal = pl.causal != 0, local = pl.local;
-    typedef void (*Kernel)(FwdParams);
-    auto go = [&](Kernel kernel) { hipLaunchKernelGGL(kernel, grid, blk, 0, s, p); };
-    // the plan's kernel in its mask mode
-    auto mode = [&](Kernel dense, Kernel causal_k, Kernel local_k) { return local ? local_k : causal ? causal_k : dense; };
+    auto go = [&](void (*kernel)(FwdParams)) { hipLaunchKernelGGL(kernel, grid, blk, 0, s, p); };
     hipError_t e = hipErrorInvalidValue;   // stays when a class or the kernel is not one of ours
-    by_dim_class(Dc, [&](auto Dk) {
-        by_dim_class(DVc, [&](auto DVk) {
-            constexpr int D = decltype(Dk)::value, DV = decltype(DVk)::value;
-            switch (pl.kernel) {
-                case kDenseFwdGeneric:
-                    go(mode(dense_fwd_generic<T, D, DV>, dense_fwd_generic<T, D, DV, true>, dense_fwd_generic<T, D, DV, false, true>));
-                    break;
-                case kDenseFwdW8B64: go(mode(dense_fwd_w8b64<T, D, DV>, causal_fwd_w8b64<T, D, DV>, local_fwd_w8b64<T, D, DV>)); break;
-                case kDenseFwdW8B64Wide:
-                    go(mode(dense_fwd_w8b64_wide<T, D, DV>, causal_fwd_w8b64_wide<T, D, DV>, local_fwd_w8b64_wide<T, D, DV>));
-                    break;
-                case kDenseFwdW8Q2:
-                    if constexpr (D <= 64 && DV <= 64) go(mode(dense_fwd_w8q2<T, D, DV>, causal_fwd_w8q2<T, D, DV>, local_fwd_w8q2<T, D, DV>));
-                    else if (local) return;   // never planned: the local two-query-block kernels exist at d, dv <= 64 only
-                    else go(dense_fwd_w8q2<T, D, DV>);
-                    break;
-                case kDenseFwdW8Q2Wide:
-                    if constexpr (D <= 64 && DV <= 64)
-                        go(mode(dense_fwd_w8q2_wide<T, D, DV>, causal_fwd_w8q2_wide<T, D, DV>, local_fwd_w8q2_wide<T, D, DV>));
-                    else if (local) return;
-                    else go(dense_fwd_w8q2_wide<T, D, DV>);
-                    break;
-                case kDenseFwdW8B64Split: go(dense_fwd_w8b64_split<T, D, DV>); break;
-                case kDenseFwdW8Q2Split: go(dense_fwd_w8q2_split<T, D, DV>); break;
-                default: return;
-            }
-            if (pl.nsplit > 1) {
-                const int64_t total = (int64_t)p.N * p.dv * p.batch;
-                hipLaunchKernelGGL(fwd_split_combine<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p, total);
-            }
-            e = hipGetLastError();
+    by_mask(pl.mask, [&](auto M) {
+        by_dim_class(Dc, [&](auto Dk) {
+            by_dim_class(DVc, [&](auto DVk) {
+                constexpr DenseMask MASK = decltype(M)::value;
+                constexpr int D = decltype(Dk)::value, DV = decltype(DVk)::value;
+                constexpr bool q2 = MASK == kMaskNone || (D <= 64 && DV <= 64);   // w8q2 exists here
+                switch (pl.kernel) {
+                    case kDenseFwdGeneric: go(dense_fwd_generic<T, D, DV, MASK>); break;
+                    case kDenseFwdW8B64: go(dense_fwd_w8b64<T, D, DV, MASK>); break;
+                    case kDenseFwdW8B64Wide: go(dense_fwd_w8b64_wide<T, D, DV, MASK>); break;
+                    case kDenseFwdW8Q2:
+                        if constexpr (q2) go(dense_fwd_w8q2<T, D, DV, MASK>);
+                        else return;   // never planned
+                        break;
+                    case kDenseFwdW8Q2Wide:
+                        if constexpr (q2) go(dense_fwd_w8q2_wide<T, D, DV, MASK>);
+                        else return;
+                        break;
+                    case kDenseFwdW8B64Split: go(dense_fwd_w8b64_split<T, D, DV>); break;
+                    case kDenseFwdW8Q2Split: go(dense_fwd_w8q2_split<T, D, DV>); break;
+                    default: return;
+                }
+                if (pl.nsplit > 1) {
+                    const int64_t total = (int64_t)p.N * p.dv * p.batch;
+                    hipLaunchKernelGGL(fwd_split_combine<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p, total);
+                }
+                e = hipGetLastError();
+            });
         });
     });
     return e;
 }
 static hipError_t launch_f32(const DenseFwdPlan& pl, const FwdParams& p, int Dc, int DVc, hipStream_t s) {
     hipError_t e = hipErrorInvalidValue;
-    by_dim_class(Dc, [&](auto Dk) {
-        by_dim_class(DVc, [&](auto DVk) {
-            constexpr int D = decltype(Dk)::value, DV = decltype(DVk)::value;
-            void (*kernel)(FwdParams) = pl.local    ? dense_fwd_generic_f32<D, DV, false, true>
-                                        : pl.causal ? dense_fwd_generic_f32<D, DV, true>
-                                                    : dense_fwd_generic_f32<D, DV>;
-            hipLaunchKernelGGL(kernel, dim3((unsigned)pl.grid), dim3(pl.block), 0, s, p);
-            e = hipGetLastError();
+    by_mask(pl.mask, [&](auto M) {
+        by_dim_class(Dc, [&](auto Dk) {
+            by_dim_class(DVc, [&](auto DVk) {
+                hipLaunchKernelGGL((dense_fwd_generic_f32<decltype(Dk)::value, decltype(DVk)::value, decltype(M)::value>),
+                                   dim3((unsigned)pl.grid), dim3(pl.block), 0, s, p);
+                e = hipGetLastError();
+            });
         });
     });
     return e;
@@ -1251,16 +1222,9 @@ static void pad_keys(const void* src, void* dst, int64_t Nk, int64_t ldk, int64_
 
 // The shape's own needs (aligned tensors, the auto variant, room for everything): the
 // queries have no pointers, and the CU count does not change the total.
-size_t dense_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    return dense_fwd_plan(dtype, N, Nk, d, dv, batch, kMaskNone, {kFwdAuto, 0}, true, true, SIZE_MAX, 0).total;
-}
-// fa_causal_fwd: the padded K / V copies only (causal launches never split the keys)
-size_t causal_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    return dense_fwd_plan(dtype, N, Nk, d, dv, batch, kMaskCausal, {kFwdAuto, 0}, true, true, SIZE_MAX, 0).total;
-}
-// fa_local_fwd: the same, whatever the window (local launches never split either)
-size_t local_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
-    return dense_fwd_plan(dtype, N, Nk, d, dv, batch, kMaskLocal, {kFwdAuto, 0}, true, true, SIZE_MAX, 0).total;
+// (A masked launch never splits the keys: its total is the padded K / V copies only.)
+size_t dense_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, DenseMask mask) {
+    return dense_fwd_plan(dtype, N, Nk, d, dv, batch, mask, {kFwdAuto, 0}, true, true, SIZE_MAX, 0).total;
 }
 
 int launch_dense_fwd(const DenseArgs& a, hipStream_t s, const char** why) {
@@ -1271,14 +1235,7 @@ int launch_dense_fwd(const DenseArgs& a, hipStream_t s, const char** why) {
         *why = "head dimension exceeds the compiled maximum (128)";
         return FA_ERR_UNSUPPORTED;
     }
-    if (a.causal && a.Nk < a.N) {
-        *why = "causal attention needs Nk >= N (a query would see no key)";
-        return FA_ERR_UNSUPPORTED;
-    }
-    if (a.local && a.Nk < a.N) {
-        *why = "local attention needs Nk >= N (a query would see no key)";
-        return FA_ERR_UNSUPPORTED;
-    }
+    if (mask_lacks_keys(a.mask, a.N, a.Nk, why)) return FA_ERR_UNSUPPORTED;
     if (a.N > INT32_MAX / 2 || a.Nk > INT32_MAX / 2 || a.N * a.d > INT32_MAX ||
         a.Nk * a.d > INT32_MAX || a.Nk * a.dv > INT32_MAX || a.N * a.dv > INT32_MAX) {
         *why = "per-slab extent exceeds 2^31 elements";
@@ -1292,7 +1249,7 @@ int launch_dense_fwd(const DenseArgs& a, hipStream_t s, const char** why) {
         *why = "unknown dtype";
         return FA_ERR_INVALID_ARG;
     }
-    const DenseFwdPlan pl = dense_fwd_plan(a.dtype, a.N, a.Nk, a.d, a.dv, a.batch, dense_mask(a.causal, a.local),
+    const DenseFwdPlan pl = dense_fwd_plan(a.dtype, a.N, a.Nk, a.d, a.dv, a.batch, a.mask,
                                            {g_fwd_variant, g_causal_rev}, aligned16(a.K) && aligned16(a.V),
                                            aligned16(a.Q) && aligned16(a.O), a.workspace ? a.workspace_bytes : 0,
                                            device_cus(s));
@@ -1308,9 +1265,10 @@ int launch_dense_fwd(const DenseArgs& a, hipStream_t s, const char** why) {
     p.rescale_log2 = g_fwd_rescale_log2;
     p.batch = (int)a.batch;
     p.nsplit = pl.nsplit; p.tps = pl.tps; p.opart = p.lpart = p.mpart = nullptr;
-    if (pl.local) {   // never split: the window rides in the split's two ints (fa_fwd_params.h)
-        p.wleft = local_clamp(a.left, a.Nk);
-        p.wright = local_clamp(a.right, a.Nk);
+    if (a.mask == kMaskLocal) {   // never split: the window rides in the split's two ints (fa_fwd_params.h)
+        const MaskInts mi = mask_ints(a.mask, a.left, a.right, a.N, a.Nk);
+        p.wleft = mi.left;
+        p.wright = mi.right;
     }
     p.causal = pl.causal;
     p.fast = pl.kv_vec;

@@ -10,6 +10,12 @@
 
 namespace fa {
 
+// The mask of a dense-family call (dense, causal, local attention are one kernel family under
+// three masks).  ONE value travels from the extern "C" entry points (api.cpp) through
+// DenseArgs / DenseBwdArgs and the plans (fa_dense_plan.h) to the kernels' single MASK
+// template parameter, which by_mask below turns into a compile-time constant.
+enum DenseMask : int { kMaskNone = 0, kMaskCausal = 1, kMaskLocal = 2 };
+
 struct DenseArgs {
     int dtype;                 // fa_dtype
     const void *Q, *K, *V;
@@ -20,10 +26,10 @@ struct DenseArgs {
     void* workspace = nullptr; // optional: padded K / V copies for ragged Nk (fa_dense_fwd_workspace)
     size_t workspace_bytes = 0;
     double scale64 = 0.0;      // Float64 kernels: τ resolved in double (0: use scale)
-    int causal = 0;            // fa_causal_fwd: query i sees keys j <= i + (Nk - N); 0: dense
-    // fa_local_fwd (never with causal): query i sees keys i + off - left <= j <= i + off + right,
-    // off = Nk - N; a negative side is unbounded (the launchers clamp: local_clamp)
-    int local = 0;
+    // kMaskCausal (fa_causal_fwd): query i sees keys j <= i + off, off = Nk - N.  kMaskLocal
+    // (fa_local_fwd): keys i + off - left <= j <= i + off + right; a negative side is unbounded
+    // (mask_ints clamps).  left / right are read under kMaskLocal only.
+    DenseMask mask = kMaskNone;
     int64_t left = -1, right = -1;
 };
 
@@ -37,8 +43,7 @@ struct DenseBwdArgs {
     void* workspace;
     size_t workspace_bytes;
     double scale64 = 0.0;      // Float64 kernels: τ resolved in double (0: use scale)
-    int causal = 0;            // fa_causal_bwd: as DenseArgs::causal (always the two-pass form)
-    int local = 0;             // fa_local_bwd: as DenseArgs::local (always the two-pass form)
+    DenseMask mask = kMaskNone;   // as DenseArgs::mask (a masked backward is always the two-pass form)
     int64_t left = -1, right = -1;
 };
 
@@ -112,17 +117,14 @@ struct SoftmaxArgs {
 
 // Each returns a hipError_t-like code through *err and a fa_status.
 int launch_dense_fwd(const DenseArgs& a, hipStream_t s, const char** why);
-size_t dense_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch);
-size_t dense_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch);
 int launch_dense_bwd(const DenseBwdArgs& a, hipStream_t s, const char** why);
-// causal (DenseArgs / DenseBwdArgs with causal = 1): the forward's padded K / V copies only
-// (no split-KV part); the backward's header, row statistics and pad plan (never the single
-// pass's running sums).  Neither asks the device.
-size_t causal_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch);
-size_t causal_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch);
-// local (DenseArgs / DenseBwdArgs with local = 1): the causal answers, whatever the window
-size_t local_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch);
-size_t local_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch);
+// The workspace a shape needs under a mask.  Causal and local (the same answers, whatever the
+// window): the forward's padded K / V copies only (no split-KV part); the backward's header,
+// row statistics and pad plan, never the single pass's running sums, so only the dense
+// backward query asks the device for its CU count.  (The windowed composed path asks for the
+// dense answers.)
+size_t dense_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, DenseMask mask = kMaskNone);
+size_t dense_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, DenseMask mask = kMaskNone);
 int dense_bwd_handoff_status(const void* workspace, size_t workspace_bytes, hipStream_t s, int* status,
                              const char** why);
 // Float64 (fa_f64.hip): the forward, and the backward's row statistics in double
@@ -169,13 +171,34 @@ inline int head_dim_class(int64_t d) {
 
 constexpr int kMaxHeadDim = 128;
 
-// The mask of a dense-family launch: which instantiation of every kernel family runs.
-enum DenseMask : int { kMaskNone = 0, kMaskCausal = 1, kMaskLocal = 2 };
-inline DenseMask dense_mask(int causal, int local) { return local ? kMaskLocal : causal ? kMaskCausal : kMaskNone; }
-// One side of a local window as the kernels take it: in [0, Nk], where Nk binds nowhere
-// (negative = unbounded, and a value >= Nk is the same).  Done on the 64-bit value, before
-// anything becomes a 32-bit int.
-inline int local_clamp(int64_t w, int64_t Nk) { return (int)(w < 0 || w > Nk ? Nk : w); }
+// "causal" / "local": the mask's word in messages and entry-point names ("dense" for kMaskNone)
+inline const char* mask_word(DenseMask mask) { return mask == kMaskLocal ? "local" : mask == kMaskCausal ? "causal" : "dense"; }
+// A masked call needs Nk >= N: true, with the mask's message in *why, when it has fewer keys.
+inline bool mask_lacks_keys(DenseMask mask, int64_t N, int64_t Nk, const char** why) {
+    if (mask == kMaskNone || Nk >= N) return false;
+    *why = mask == kMaskLocal ? "local attention needs Nk >= N (a query would see no key)"
+                              : "causal attention needs Nk >= N (a query would see no key)";
+    return true;
+}
+// The mask as the five ints of the device parameter structs (BwdParams, F64Params; FwdParams
+// takes the window only).  off = Nk - N of the caller's extents.  A side of the local window
+// lands in [0, Nk], where Nk binds nowhere (negative = unbounded, and a value >= Nk is the
+// same), clamped on the 64-bit value before it becomes a 32-bit int.
+struct MaskInts {
+    int causal = 0, off = 0, local = 0, left = 0, right = 0;
+};
+inline MaskInts mask_ints(DenseMask mask, int64_t left, int64_t right, int64_t N, int64_t Nk) {
+    MaskInts r;
+    if (mask == kMaskNone) return r;
+    r.off = (int)(Nk - N);
+    r.causal = mask == kMaskCausal;
+    if (mask == kMaskLocal) {
+        r.local = 1;
+        r.left = (int)(left < 0 || left > Nk ? Nk : left);
+        r.right = (int)(right < 0 || right > Nk ? Nk : right);
+    }
+    return r;
+}
 
 // Workspace regions start on 256-B boundaries; the vector paths want 16-B aligned tensors.
 inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -184,9 +207,9 @@ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 // A run-time head-dim class as a compile-time constant for the launchers: by_dim_class calls
 // f(dim_c<C>{}) with the class c (32, 64 or 128; false, and no call, for anything else).  f
-// is a generic lambda, [&](auto D), that names kernel<..., D> or decltype(D)::value.  (A
-// CAUSAL twin needs no such dispatcher: kernels of one signature are picked as function
-// pointers, causal ? kernel<..., true> : kernel<...>.)
+// is a generic lambda, [&](auto D), that names kernel<..., D> or decltype(D)::value.
+// by_mask does the same for a DenseMask: f(mask_c<M>{}), [&](auto M) names
+// kernel<..., decltype(M)::value>.
 template <int N>
 using dim_c = std::integral_constant<int, N>;
 template <class F>
@@ -195,6 +218,17 @@ inline bool by_dim_class(int c, F&& f) {
         case 32: f(dim_c<32>{}); return true;
         case 64: f(dim_c<64>{}); return true;
         case 128: f(dim_c<128>{}); return true;
+    }
+    return false;
+}
+template <DenseMask M>
+using mask_c = std::integral_constant<DenseMask, M>;
+template <class F>
+inline bool by_mask(DenseMask mask, F&& f) {
+    switch (mask) {
+        case kMaskNone: f(mask_c<kMaskNone>{}); return true;
+        case kMaskCausal: f(mask_c<kMaskCausal>{}); return true;
+        case kMaskLocal: f(mask_c<kMaskLocal>{}); return true;
     }
     return false;
 }

@@ -342,24 +342,20 @@ def dense_fa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float = 0
 
 
 # ----------------------------------------------------------------------------
-# causal dense
+# causal and local (sliding window around the causal diagonal) dense attention: one
+# implementation each, parameterised by the mask's name ("causal" / "local", as in the C
+# ABI's fa_<mask>_fwd ...) and its window: () for causal, (left, right) for local
 # ----------------------------------------------------------------------------
-def _causal_extents(N: int, Nk: int) -> None:
+def _masked_extents(mask: str, N: int, Nk: int) -> None:
     """The C ABI's rule, raised before any device is touched."""
     if Nk < N:
         raise FlashAttentionError(FA_ERR_UNSUPPORTED,
-                                  f"causal attention needs Nk >= N (got N = {N}, Nk = {Nk}): a query would see no key")
+                                  f"{mask} attention needs Nk >= N (got N = {N}, Nk = {Nk}): a query would see no key")
 
 
-def causal_fa_(O: torch.Tensor, l: torch.Tensor, m: torch.Tensor,
-               Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor,
-               scale: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """Causal ``dense_fa!``, in place: query i attends the keys j <= i + (Nk - N)
-    (bottom-right aligned: the last query sees every key; N == Nk is the lower
-    triangle).  Q (N, d, B), K (Nk, d, B), V (Nk, dv, B), O (N, dv, B); l, m (N, 1, B)
-    float32 over the visible keys.  Nk < N raises FlashAttentionError (unsupported)."""
+def _masked_fa_(mask: str, window: Tuple[int, ...], O, l, m, Q, K, V, scale: float):
     for t in (O, l, m, Q, K, V):
-        _require(t.dim() == 3, "causal_fa! expects 3-D (N, d, batch) arrays")
+        _require(t.dim() == 3, f"{mask}_fa! expects 3-D (N, d, batch) arrays")
     N, d, B = Q.shape
     Nk, dv = K.shape[0], V.shape[1]
     _require(K.shape == (Nk, d, B), f"K has shape {tuple(K.shape)}, expected ({Nk}, {d}, {B})")
@@ -368,34 +364,28 @@ def causal_fa_(O: torch.Tensor, l: torch.Tensor, m: torch.Tensor,
     _require(l.shape == (N, 1, B) and m.shape == (N, 1, B), "l, m must be (N, 1, batch)")
     _require(l.dtype == torch.float32 and m.dtype == torch.float32, "l, m must be float32")
     code = _dtype_code(Q, K, V, O)
-    _causal_extents(N, Nk)
+    _masked_extents(mask, N, Nk)
     _device_check(Q, K, V, O, l, m)
     Lb = lib()
-    nws = Lb.fa_causal_fwd_workspace(code, N, Nk, d, dv, B)
+    nws = getattr(Lb, f"fa_{mask}_fwd_workspace")(code, N, Nk, d, dv, B)
     ws = _workspace(Q.device, nws) if nws else None
-    _check(Lb.fa_causal_fwd(code, _ptr(Q), _ptr(K), _ptr(V), _ptr(O), _ptr(l), _ptr(m),
-                            N, Nk, d, dv, B, float(scale), _ptr(ws), int(nws), _stream(Q)))
+    _check(getattr(Lb, f"fa_{mask}_fwd")(code, _ptr(Q), _ptr(K), _ptr(V), _ptr(O), _ptr(l), _ptr(m),
+                                         N, Nk, d, dv, B, *map(int, window), float(scale), _ptr(ws), int(nws), _stream(Q)))
     return O, l, m
 
 
-def causal_fa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float = 0.0):
-    """``causal_fa(q, k, v) -> (O, l, m)``: :func:`causal_fa_` on fresh outputs.
-    q (N, d, B), k (Nk, d, B), v (Nk, dv, B) with Nk >= N."""
-    _require(q.dim() == 3 and k.dim() == 3 and v.dim() == 3, "causal_fa expects 3-D (N, d, batch) arrays")
+def _masked_fa(mask: str, window: Tuple[int, ...], q, k, v, scale: float):
+    _require(q.dim() == 3 and k.dim() == 3 and v.dim() == 3, f"{mask}_fa expects 3-D (N, d, batch) arrays")
     N, d, B = q.shape
     O = jl_empty((N, v.shape[1], B), q.dtype, q.device)
     l = jl_empty((N, 1, B), torch.float32, q.device)
     m = jl_empty((N, 1, B), torch.float32, q.device)
-    return causal_fa_(O, l, m, q, k, v, scale)
+    return _masked_fa_(mask, window, O, l, m, q, k, v, scale)
 
 
-def causal_fa_backward(Q, K, V, O, dO, l, m, scale: float = 0.0):
-    """Backward of :func:`causal_fa`: returns ``(dQ, dK, dV)``.  O, l, m are the
-    forward's outputs.  Always the two-pass form (no atomics, no hand-off), so all
-    three gradients are bitwise reproducible; :func:`backward_handoff_status` reads
-    -1 after it."""
+def _masked_fa_backward(mask: str, window: Tuple[int, ...], Q, K, V, O, dO, l, m, scale: float):
     for t in (Q, K, V, O, dO, l, m):
-        _require(t.dim() == 3, "causal_fa_backward expects 3-D (N, d, batch) arrays")
+        _require(t.dim() == 3, f"{mask}_fa_backward expects 3-D (N, d, batch) arrays")
     N, d, B = Q.shape
     Nk, dv = K.shape[0], V.shape[1]
     _require(K.shape == (Nk, d, B) and V.shape == (Nk, dv, B), "K, V shapes disagree with Q")
@@ -403,134 +393,30 @@ def causal_fa_backward(Q, K, V, O, dO, l, m, scale: float = 0.0):
     _require(l.shape == (N, 1, B) and m.shape == (N, 1, B), "l, m must be (N, 1, batch)")
     _require(l.dtype == torch.float32 and m.dtype == torch.float32, "l, m must be float32")
     code = _dtype_code(Q, K, V, O, dO)
-    _causal_extents(N, Nk)
+    _masked_extents(mask, N, Nk)
     _device_check(Q, K, V, O, dO, l, m)
     dQ = jl_empty((N, d, B), Q.dtype, Q.device)
     dK = jl_empty((Nk, d, B), Q.dtype, Q.device)
     dV = jl_empty((Nk, dv, B), Q.dtype, Q.device)
     L = lib()
-    nws = L.fa_causal_bwd_workspace(code, N, Nk, d, dv, B)
-    ws = _workspace(Q.device, nws, entry="causal_fa_backward")
-    _check(L.fa_causal_bwd(code, _ptr(Q), _ptr(K), _ptr(V), _ptr(O), _ptr(dO), _ptr(l), _ptr(m),
-                           _ptr(dQ), _ptr(dK), _ptr(dV), N, Nk, d, dv, B, float(scale),
-                           _ptr(ws), int(nws), _stream(Q)))
+    nws = getattr(L, f"fa_{mask}_bwd_workspace")(code, N, Nk, d, dv, B)
+    ws = _workspace(Q.device, nws, entry=f"{mask}_fa_backward")
+    _check(getattr(L, f"fa_{mask}_bwd")(code, _ptr(Q), _ptr(K), _ptr(V), _ptr(O), _ptr(dO), _ptr(l), _ptr(m),
+                                        _ptr(dQ), _ptr(dK), _ptr(dV), N, Nk, d, dv, B, *map(int, window), float(scale),
+                                        _ptr(ws), int(nws), _stream(Q)))
     return dQ, dK, dV
 
 
-def causal_dpa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float = 0.0):
-    """``causal_dpa(q, k, v) -> (O, P)``: the materialising form of :func:`causal_fa`, in the
-    style of :func:`dense_dpa`: S = τ Q Kᵀ by a library GEMM, −∞ where j > i + (Nk − N),
-    P = softmax over the keys by this library's fa_softmax kernel (dims = 2; exactly 0 above
-    the diagonal), O = P V.  P is (N, Nk, B) in the input dtype; memory is O(N·Nk·B)."""
-    _require(q.dim() == 3 and k.dim() == 3 and v.dim() == 3, "causal_dpa expects 3-D (N, d, batch) arrays")
+def _masked_dpa(mask: str, left: int, right: int, q, k, v, scale: float):
+    """S = τ Q Kᵀ by a library GEMM, −∞ outside i + off − left <= j <= i + off + right (a
+    negative side unbounded; causal is (−1, 0)), softmax by fa_softmax, O = P V."""
+    _require(q.dim() == 3 and k.dim() == 3 and v.dim() == 3, f"{mask}_dpa expects 3-D (N, d, batch) arrays")
     N, d, B = q.shape
     Nk, dv = k.shape[0], v.shape[1]
     _require(k.shape == (Nk, d, B) and v.shape == (Nk, dv, B),
              "DimensionMismatch: k must match q's feature and batch dims, v k's token count and the batch dim")
     _dtype_code(q, k, v)
-    _causal_extents(N, Nk)
-    _device_check(q, k, v)
-    tau = float(scale) if scale > 0 else 1.0 / math.sqrt(d)
-    Qr, Kr, Vr = _rm(q), _rm(k), _rm(v)       # [B][d][N], [B][d][Nk], [B][dv][Nk]
-    St = torch.bmm(Kr.transpose(1, 2), Qr)    # [B][Nk][N] = column-major (N, Nk, B): P's layout
-    St.mul_(tau)
-    j = torch.arange(Nk, device=q.device)[:, None]
-    i = torch.arange(N, device=q.device)[None, :]
-    St.masked_fill_((j > i + (Nk - N))[None], float("-inf"))
-    P = _rm(St)                               # (N, Nk, B) view
-    fused_softmax_(P, P, dims=2)
-    O = _rm(torch.bmm(Vr, St))                # [B][dv][N] = column-major (N, dv, B)
-    return O, P
-
-
-# ----------------------------------------------------------------------------
-# local (sliding window around the causal diagonal)
-# ----------------------------------------------------------------------------
-def _local_extents(N: int, Nk: int) -> None:
-    """The C ABI's rule, raised before any device is touched."""
-    if Nk < N:
-        raise FlashAttentionError(FA_ERR_UNSUPPORTED,
-                                  f"local attention needs Nk >= N (got N = {N}, Nk = {Nk}): a query would see no key")
-
-
-def local_fa_(O: torch.Tensor, l: torch.Tensor, m: torch.Tensor,
-              Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor,
-              left: int, right: int, scale: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """Sliding-window ``dense_fa!``, in place: with off = Nk - N, query i attends the keys
-    i + off - left <= j <= i + off + right (0 <= j < Nk).  A negative ``left`` / ``right``
-    means no bound on that side: (-1, 0) is :func:`causal_fa_`'s mask, (-1, -1)
-    :func:`dense_fa_`'s, (0, 0) one key per query.  Shapes as :func:`causal_fa_`; l, m
-    float32 over the visible keys.  Nk < N raises FlashAttentionError (unsupported)."""
-    for t in (O, l, m, Q, K, V):
-        _require(t.dim() == 3, "local_fa! expects 3-D (N, d, batch) arrays")
-    N, d, B = Q.shape
-    Nk, dv = K.shape[0], V.shape[1]
-    _require(K.shape == (Nk, d, B), f"K has shape {tuple(K.shape)}, expected ({Nk}, {d}, {B})")
-    _require(V.shape == (Nk, dv, B), f"V has shape {tuple(V.shape)}, expected ({Nk}, {dv}, {B})")
-    _require(O.shape == (N, dv, B), f"O has shape {tuple(O.shape)}, expected ({N}, {dv}, {B})")
-    _require(l.shape == (N, 1, B) and m.shape == (N, 1, B), "l, m must be (N, 1, batch)")
-    _require(l.dtype == torch.float32 and m.dtype == torch.float32, "l, m must be float32")
-    code = _dtype_code(Q, K, V, O)
-    _local_extents(N, Nk)
-    _device_check(Q, K, V, O, l, m)
-    Lb = lib()
-    nws = Lb.fa_local_fwd_workspace(code, N, Nk, d, dv, B)
-    ws = _workspace(Q.device, nws) if nws else None
-    _check(Lb.fa_local_fwd(code, _ptr(Q), _ptr(K), _ptr(V), _ptr(O), _ptr(l), _ptr(m),
-                           N, Nk, d, dv, B, int(left), int(right), float(scale), _ptr(ws), int(nws), _stream(Q)))
-    return O, l, m
-
-
-def local_fa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, left: int, right: int, scale: float = 0.0):
-    """``local_fa(q, k, v, left, right) -> (O, l, m)``: :func:`local_fa_` on fresh outputs.
-    q (N, d, B), k (Nk, d, B), v (Nk, dv, B) with Nk >= N."""
-    _require(q.dim() == 3 and k.dim() == 3 and v.dim() == 3, "local_fa expects 3-D (N, d, batch) arrays")
-    N, d, B = q.shape
-    O = jl_empty((N, v.shape[1], B), q.dtype, q.device)
-    l = jl_empty((N, 1, B), torch.float32, q.device)
-    m = jl_empty((N, 1, B), torch.float32, q.device)
-    return local_fa_(O, l, m, q, k, v, left, right, scale)
-
-
-def local_fa_backward(Q, K, V, O, dO, l, m, left: int, right: int, scale: float = 0.0):
-    """Backward of :func:`local_fa` for the same window: returns ``(dQ, dK, dV)``.  O, l, m
-    are the forward's outputs.  Always the two-pass form, so all three gradients are bitwise
-    reproducible; keys that no query sees get dK = dV = 0."""
-    for t in (Q, K, V, O, dO, l, m):
-        _require(t.dim() == 3, "local_fa_backward expects 3-D (N, d, batch) arrays")
-    N, d, B = Q.shape
-    Nk, dv = K.shape[0], V.shape[1]
-    _require(K.shape == (Nk, d, B) and V.shape == (Nk, dv, B), "K, V shapes disagree with Q")
-    _require(O.shape == (N, dv, B) and dO.shape == (N, dv, B), "O, dO must be (N, dv, batch)")
-    _require(l.shape == (N, 1, B) and m.shape == (N, 1, B), "l, m must be (N, 1, batch)")
-    _require(l.dtype == torch.float32 and m.dtype == torch.float32, "l, m must be float32")
-    code = _dtype_code(Q, K, V, O, dO)
-    _local_extents(N, Nk)
-    _device_check(Q, K, V, O, dO, l, m)
-    dQ = jl_empty((N, d, B), Q.dtype, Q.device)
-    dK = jl_empty((Nk, d, B), Q.dtype, Q.device)
-    dV = jl_empty((Nk, dv, B), Q.dtype, Q.device)
-    L = lib()
-    nws = L.fa_local_bwd_workspace(code, N, Nk, d, dv, B)
-    ws = _workspace(Q.device, nws, entry="local_fa_backward")
-    _check(L.fa_local_bwd(code, _ptr(Q), _ptr(K), _ptr(V), _ptr(O), _ptr(dO), _ptr(l), _ptr(m),
-                          _ptr(dQ), _ptr(dK), _ptr(dV), N, Nk, d, dv, B, int(left), int(right), float(scale),
-                          _ptr(ws), int(nws), _stream(Q)))
-    return dQ, dK, dV
-
-
-def local_dpa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, left: int, right: int, scale: float = 0.0):
-    """``local_dpa(q, k, v, left, right) -> (O, P)``: the materialising form of :func:`local_fa`,
-    in :func:`causal_dpa`'s style: S = τ Q Kᵀ by a library GEMM, −∞ outside the window,
-    P = softmax over the keys by this library's fa_softmax kernel (dims = 2; exactly 0 outside
-    the window), O = P V.  P is (N, Nk, B) in the input dtype; memory is O(N·Nk·B)."""
-    _require(q.dim() == 3 and k.dim() == 3 and v.dim() == 3, "local_dpa expects 3-D (N, d, batch) arrays")
-    N, d, B = q.shape
-    Nk, dv = k.shape[0], v.shape[1]
-    _require(k.shape == (Nk, d, B) and v.shape == (Nk, dv, B),
-             "DimensionMismatch: k must match q's feature and batch dims, v k's token count and the batch dim")
-    _dtype_code(q, k, v)
-    _local_extents(N, Nk)
+    _masked_extents(mask, N, Nk)
     _device_check(q, k, v)
     tau = float(scale) if scale > 0 else 1.0 / math.sqrt(d)
     Qr, Kr, Vr = _rm(q), _rm(k), _rm(v)       # [B][d][N], [B][d][Nk], [B][dv][Nk]
@@ -548,6 +434,70 @@ def local_dpa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, left: int, righ
     fused_softmax_(P, P, dims=2)
     O = _rm(torch.bmm(Vr, St))                # [B][dv][N] = column-major (N, dv, B)
     return O, P
+
+
+def causal_fa_(O: torch.Tensor, l: torch.Tensor, m: torch.Tensor,
+               Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor,
+               scale: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Causal ``dense_fa!``, in place: query i attends the keys j <= i + (Nk - N)
+    (bottom-right aligned: the last query sees every key; N == Nk is the lower
+    triangle).  Q (N, d, B), K (Nk, d, B), V (Nk, dv, B), O (N, dv, B); l, m (N, 1, B)
+    float32 over the visible keys.  Nk < N raises FlashAttentionError (unsupported)."""
+    return _masked_fa_("causal", (), O, l, m, Q, K, V, scale)
+
+
+def causal_fa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float = 0.0):
+    """``causal_fa(q, k, v) -> (O, l, m)``: :func:`causal_fa_` on fresh outputs.
+    q (N, d, B), k (Nk, d, B), v (Nk, dv, B) with Nk >= N."""
+    return _masked_fa("causal", (), q, k, v, scale)
+
+
+def causal_fa_backward(Q, K, V, O, dO, l, m, scale: float = 0.0):
+    """Backward of :func:`causal_fa`: returns ``(dQ, dK, dV)``.  O, l, m are the
+    forward's outputs.  Always the two-pass form (no atomics, no hand-off), so all
+    three gradients are bitwise reproducible; :func:`backward_handoff_status` reads
+    -1 after it."""
+    return _masked_fa_backward("causal", (), Q, K, V, O, dO, l, m, scale)
+
+
+def causal_dpa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float = 0.0):
+    """``causal_dpa(q, k, v) -> (O, P)``: the materialising form of :func:`causal_fa`, in the
+    style of :func:`dense_dpa`: S = τ Q Kᵀ by a library GEMM, −∞ where j > i + (Nk − N),
+    P = softmax over the keys by this library's fa_softmax kernel (dims = 2; exactly 0 above
+    the diagonal), O = P V.  P is (N, Nk, B) in the input dtype; memory is O(N·Nk·B)."""
+    return _masked_dpa("causal", -1, 0, q, k, v, scale)
+
+
+def local_fa_(O: torch.Tensor, l: torch.Tensor, m: torch.Tensor,
+              Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor,
+              left: int, right: int, scale: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Sliding-window ``dense_fa!``, in place: with off = Nk - N, query i attends the keys
+    i + off - left <= j <= i + off + right (0 <= j < Nk).  A negative ``left`` / ``right``
+    means no bound on that side: (-1, 0) is :func:`causal_fa_`'s mask, (-1, -1)
+    :func:`dense_fa_`'s, (0, 0) one key per query.  Shapes as :func:`causal_fa_`; l, m
+    float32 over the visible keys.  Nk < N raises FlashAttentionError (unsupported)."""
+    return _masked_fa_("local", (left, right), O, l, m, Q, K, V, scale)
+
+
+def local_fa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, left: int, right: int, scale: float = 0.0):
+    """``local_fa(q, k, v, left, right) -> (O, l, m)``: :func:`local_fa_` on fresh outputs.
+    q (N, d, B), k (Nk, d, B), v (Nk, dv, B) with Nk >= N."""
+    return _masked_fa("local", (left, right), q, k, v, scale)
+
+
+def local_fa_backward(Q, K, V, O, dO, l, m, left: int, right: int, scale: float = 0.0):
+    """Backward of :func:`local_fa` for the same window: returns ``(dQ, dK, dV)``.  O, l, m
+    are the forward's outputs.  Always the two-pass form, so all three gradients are bitwise
+    reproducible; keys that no query sees get dK = dV = 0."""
+    return _masked_fa_backward("local", (left, right), Q, K, V, O, dO, l, m, scale)
+
+
+def local_dpa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, left: int, right: int, scale: float = 0.0):
+    """``local_dpa(q, k, v, left, right) -> (O, P)``: the materialising form of :func:`local_fa`,
+    in :func:`causal_dpa`'s style: S = τ Q Kᵀ by a library GEMM, −∞ outside the window,
+    P = softmax over the keys by this library's fa_softmax kernel (dims = 2; exactly 0 outside
+    the window), O = P V.  P is (N, Nk, B) in the input dtype; memory is O(N·Nk·B)."""
+    return _masked_dpa("local", left, right, q, k, v, scale)
 
 
 def circulant_fa_(O: torch.Tensor, l: torch.Tensor, m: torch.Tensor,

@@ -158,6 +158,60 @@ def test_invalid_arguments_return_status_and_message():
         assert rc == fa_hip.FA_ERR_WORKSPACE
 
 
+def test_dense_entry_points_differ_from_the_masked_ones_in_these_ways():
+    """What fa_dense_fwd, fa_dense_fwd_ws and fa_dense_bwd do that fa_causal_* / fa_local_* do
+    not (tests/test_causal_host.py, test_local_host.py pin those): the empty-input rules, no
+    shape check before the workspace check (the launchers refuse afterwards, in their own
+    words), Nk < N accepted.  Every call here returns before a launch or a device call."""
+    import fa_hip
+    L = fa_hip.lib()
+    P, N6, N10 = ctypes.c_void_p(16), [None] * 6, [None] * 10
+    BIG = ctypes.c_size_t(1 << 40)
+    err = lambda: L.fa_last_error()
+    # forward, no query: a no-op with null pointers, also through fa_dense_fwd_ws
+    assert L.fa_dense_fwd_ws(1, *N6, 0, 4, 4, 4, 1, 0.0, None, 0, None) == 0
+    assert L.fa_dense_fwd_ws(1, *N6, 4, 0, 4, 4, 0, 0.0, None, 0, None) == 0 and err() == b""
+    # forward, no key: O, l, m are filled, so null outputs are rejected (and only then)
+    assert L.fa_dense_fwd(1, *N6, 4, 0, 4, 4, 1, 0.0, None) == fa_hip.FA_ERR_INVALID_ARG
+    assert err() == b"fa_dense_fwd: null pointer"
+    assert L.fa_dense_fwd_ws(1, P, P, P, None, P, P, 4, 0, 4, 4, 1, 0.0, None, 0, None) == fa_hip.FA_ERR_INVALID_ARG
+    assert err() == b"fa_dense_fwd_ws: null pointer"
+    # dtype, then DimensionMismatch, come before the empty-input rules
+    assert L.fa_dense_fwd(9, *N6, 0, 4, 0, 4, 1, 0.0, None) == fa_hip.FA_ERR_INVALID_ARG and b"dtype" in err()
+    assert L.fa_dense_fwd(1, *N6, 0, 4, 0, 4, 1, 0.0, None) == fa_hip.FA_ERR_INVALID_ARG and b"DimensionMismatch" in err()
+    # backward, empty: the gradients that have elements are zero-filled, so null is rejected
+    # for those only; with none it is a no-op
+    bwd = lambda ptrs, N, Nk, B, ws=None, nws=0, d=4: L.fa_dense_bwd(1, *ptrs, N, Nk, d, 4, B, 0.0, ws, nws, None)
+    assert bwd(N10, 0, 0, 1) == 0 and bwd(N10, 4, 4, 0) == 0 and err() == b""
+    assert bwd(N10, 0, 4, 1) == fa_hip.FA_ERR_INVALID_ARG and err() == b"fa_dense_bwd: null pointer"   # dK, dV
+    assert bwd(N10, 4, 0, 1) == fa_hip.FA_ERR_INVALID_ARG and err() == b"fa_dense_bwd: null pointer"   # dQ
+    assert bwd([P] * 7 + [P, None, P], 0, 4, 1) == fa_hip.FA_ERR_INVALID_ARG                            # dK alone
+    assert L.fa_dense_bwd(9, *N10, 0, 4, 4, 4, 1, 0.0, None, 0, None) == fa_hip.FA_ERR_INVALID_ARG and b"dtype" in err()
+    # the workspace check precedes every shape refusal, which is the launcher's: head dimension
+    assert L.fa_dense_fwd_workspace(1, 64, 63, 129, 32, 1) > 0          # Nk < N is a dense shape
+    assert L.fa_dense_fwd_ws(1, *[P] * 6, 64, 63, 129, 32, 1, 0.0, None, 0, None) == fa_hip.FA_ERR_WORKSPACE
+    assert err() == b"fa_dense_fwd_ws: workspace missing or smaller than fa_dense_fwd_workspace()"
+    assert L.fa_dense_fwd_ws(1, *[P] * 6, 64, 63, 129, 32, 1, 0.0, P, BIG, None) == fa_hip.FA_ERR_UNSUPPORTED
+    assert err().startswith(b"fa_dense_fwd_ws: head dimension")
+    assert L.fa_dense_fwd(1, *[P] * 6, 64, 63, 129, 32, 1, 0.0, None) == fa_hip.FA_ERR_UNSUPPORTED   # no workspace to check
+    assert err().startswith(b"fa_dense_fwd: head dimension")
+    assert L.fa_dense_bwd_workspace(1, 64, 63, 129, 4, 1) > 0
+    assert bwd([P] * 10, 64, 63, 1, d=129) == fa_hip.FA_ERR_WORKSPACE
+    assert err() == b"fa_dense_bwd: workspace missing or smaller than fa_dense_bwd_workspace()"
+    assert bwd([P] * 10, 64, 63, 1, P, BIG, d=129) == fa_hip.FA_ERR_UNSUPPORTED and err().startswith(b"fa_dense_bwd: head dimension")
+    # ... and the extents, in the launchers' words (the masked entry points say "32-bit addressing");
+    # a forward that needs no workspace passes the check without one
+    assert L.fa_dense_fwd_workspace(1, 1 << 30, 1 << 30, 4, 4, 1) == 0
+    assert L.fa_dense_fwd_ws(1, *[P] * 6, 1 << 30, 1 << 30, 4, 4, 1, 0.0, None, 0, None) == fa_hip.FA_ERR_UNSUPPORTED
+    assert err() == b"fa_dense_fwd_ws: per-slab extent exceeds 2^31 elements"
+    assert bwd([P] * 10, 1 << 30, 1 << 30, 1, P, BIG) == fa_hip.FA_ERR_UNSUPPORTED
+    assert err() == b"fa_dense_bwd: extent exceeds 2^31 elements"
+    # the queries answer 0 for non-positive extents only
+    for q in (L.fa_dense_fwd_workspace, L.fa_dense_bwd_workspace):
+        assert q(1, 0, 63, 64, 64, 1) == 0 and q(1, 64, 0, 64, 64, 1) == 0 and q(1, 64, 63, 64, 64, 0) == 0
+        assert q(1, 64, 63, 64, 64, 1) > 0
+
+
 def test_last_error_is_thread_local():
     import fa_hip
     L = fa_hip.lib()

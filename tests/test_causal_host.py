@@ -117,6 +117,37 @@ def test_abi_rejections_carry_status_and_message():
         assert rc == fa_hip.FA_ERR_UNSUPPORTED and b"32-bit" in L.fa_last_error()
 
 
+def test_abi_check_order_and_names():
+    """dtype, DimensionMismatch, empty inputs, null pointer, head dimension, Nk >= N, 32-bit
+    extents, workspace: each check wins over every later one, and fa_last_error() begins with
+    the function's own name."""
+    L = fa_hip.lib()
+    for call, n, name in ((_fwd, 6, b"fa_causal_fwd: "), (_bwd, 10, b"fa_causal_bwd: ")):
+        bad = [None] + [P16] * (n - 1)
+        assert call(L, 9, [None] * n, 0, 64, 0, 32, 1) == fa_hip.FA_ERR_INVALID_ARG
+        assert L.fa_last_error() == name + b"unknown dtype"
+        assert call(L, 1, [None] * n, 0, 64, 0, 32, 1) == fa_hip.FA_ERR_INVALID_ARG      # over the empty no-op
+        assert L.fa_last_error().startswith(name + b"DimensionMismatch")
+        assert call(L, 1, [None] * n, 0, 64, 129, 32, 1) == 0                              # empty over everything later
+        for N, Nk, d in ((64, 64, 129), (64, 63, 32), (1 << 30, 1 << 30, 4)):              # null over the shape checks
+            assert call(L, 1, bad, N, Nk, d, 32, 1) == fa_hip.FA_ERR_INVALID_ARG
+            assert L.fa_last_error() == name + b"null pointer"
+        assert call(L, 1, [P16] * n, 64, 63, 129, 32, 1) == fa_hip.FA_ERR_UNSUPPORTED       # head dimension over Nk >= N
+        assert L.fa_last_error().startswith(name + b"head dimension")
+        assert call(L, 1, [P16] * n, 1 << 30, (1 << 30) - 1, 4, 4, 1) == fa_hip.FA_ERR_UNSUPPORTED   # Nk >= N over the extents
+        assert L.fa_last_error() == name + b"causal attention needs Nk >= N (a query would see no key)"
+        assert call(L, 1, [P16] * n, 1 << 30, 1 << 30, 4, 4, 1) == fa_hip.FA_ERR_UNSUPPORTED          # extents over the workspace
+        assert L.fa_last_error() == name + b"extent exceeds the kernels' 32-bit addressing"
+    # the backward rejects a null workspace even when told it holds the bytes; the forward
+    # rejects a missing one only when the shape needs one
+    need = L.fa_causal_bwd_workspace(1, 256, 256, 64, 64, 2)
+    assert _bwd(L, 1, [P16] * 10, 256, 256, 64, 64, 2, None, need) == fa_hip.FA_ERR_WORKSPACE
+    assert L.fa_last_error() == b"fa_causal_bwd: workspace missing or smaller than fa_causal_bwd_workspace()"
+    need = L.fa_causal_fwd_workspace(1, 250, 250, 64, 64, 2)
+    assert _fwd(L, 1, [P16] * 6, 250, 250, 64, 64, 2, None, need) == fa_hip.FA_ERR_WORKSPACE
+    assert L.fa_last_error() == b"fa_causal_fwd: workspace missing or smaller than fa_causal_fwd_workspace()"
+
+
 def test_abi_workspace_is_checked_before_any_launch():
     L = fa_hip.lib()
     need = L.fa_causal_bwd_workspace(1, 256, 256, 64, 64, 2)

@@ -156,6 +156,32 @@ def test_abi_rejections_carry_status_and_message_in_the_causal_order():
         assert b"fa_local_" in L.fa_last_error()
 
 
+def test_abi_check_order_and_names():
+    """As the causal pair's (tests/test_causal_host.py): each check wins over every later one,
+    fa_last_error() begins with the function's own name, and the Nk >= N message says "local"."""
+    L = fa_hip.lib()
+    for call, n, name in ((_fwd, 6, b"fa_local_fwd: "), (_bwd, 10, b"fa_local_bwd: ")):
+        bad = [None] + [P16] * (n - 1)
+        assert call(L, 9, [None] * n, 0, 64, 0, 32, 1) == fa_hip.FA_ERR_INVALID_ARG
+        assert L.fa_last_error() == name + b"unknown dtype"
+        assert call(L, 1, [None] * n, 0, 64, 0, 32, 1) == fa_hip.FA_ERR_INVALID_ARG      # over the empty no-op
+        assert L.fa_last_error().startswith(name + b"DimensionMismatch")
+        assert call(L, 1, [None] * n, 0, 64, 129, 32, 1) == 0                              # empty over everything later
+        for N, Nk, d in ((64, 64, 129), (64, 63, 32), (1 << 30, 1 << 30, 4)):              # null over the shape checks
+            assert call(L, 1, bad, N, Nk, d, 32, 1) == fa_hip.FA_ERR_INVALID_ARG
+            assert L.fa_last_error() == name + b"null pointer"
+        assert call(L, 1, [P16] * n, 1 << 30, (1 << 30) - 1, 4, 4, 1) == fa_hip.FA_ERR_UNSUPPORTED   # Nk >= N over the extents
+        assert L.fa_last_error() == name + b"local attention needs Nk >= N (a query would see no key)"
+        assert call(L, 1, [P16] * n, 1 << 30, 1 << 30, 4, 4, 1) == fa_hip.FA_ERR_UNSUPPORTED          # extents over the workspace
+        assert L.fa_last_error() == name + b"extent exceeds the kernels' 32-bit addressing"
+    need = L.fa_local_bwd_workspace(1, 256, 256, 64, 64, 2)
+    assert _bwd(L, 1, [P16] * 10, 256, 256, 64, 64, 2, None, need) == fa_hip.FA_ERR_WORKSPACE     # null, whatever the bytes
+    assert L.fa_last_error() == b"fa_local_bwd: workspace missing or smaller than fa_local_bwd_workspace()"
+    need = L.fa_local_fwd_workspace(1, 250, 250, 64, 64, 2)
+    assert _fwd(L, 1, [P16] * 6, 250, 250, 64, 64, 2, None, need) == fa_hip.FA_ERR_WORKSPACE
+    assert L.fa_last_error() == b"fa_local_fwd: workspace missing or smaller than fa_local_fwd_workspace()"
+
+
 def test_abi_workspace_is_checked_before_any_launch_and_names_the_query():
     L = fa_hip.lib()
     need = L.fa_local_bwd_workspace(1, 256, 256, 64, 64, 2)
@@ -237,6 +263,35 @@ def test_plan_hooks_answer_without_a_device():
     assert L.fa_debug_local_bwd_plan(1, 512, 512, 64, 64, 1, 0, AMPLE, 256, b) == 1   # misaligned: generic
     assert L.fa_debug_local_bwd_plan(0, 500, 500, 64, 64, 1, 1, AMPLE, 256, b) == 2   # fp32 MFMA
     assert L.fa_debug_local_bwd_plan(3, 500, 500, 64, 64, 1, 1, AMPLE, 256, b) == 0   # Float64
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=["-".join(map(str, s)) for s in SHAPES])
+def test_dense_plan_hooks_at_mask_2_agree_with_the_local_hooks(shape):
+    """fa_debug_dense_fwd_plan / fa_debug_dense_bwd_plan read their `causal` argument as the
+    mask (0 dense, 1 causal, 2 local): at 2, under the default knobs, they return the local
+    hooks' kernel and every field both report, with and without room in the workspace, with
+    aligned and misaligned tensors."""
+    L = fa_hip.lib()
+    ci, i64, sz, out_p = ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int64)
+    L.fa_debug_dense_fwd_plan.restype = L.fa_debug_dense_bwd_plan.restype = ci
+    L.fa_debug_dense_fwd_plan.argtypes = [ci] + [i64] * 5 + [ci] * 5 + [sz, ci, out_p]
+    L.fa_debug_dense_bwd_plan.argtypes = [ci] + [i64] * 5 + [ci] * 6 + [sz, ci, out_p]
+    lf, lb = (ctypes.c_int64 * 8)(), (ctypes.c_int64 * 6)()
+    df, db = (ctypes.c_int64 * 17)(), (ctypes.c_int64 * 25)()
+    for nws in (1 << 40, 0):
+        for al in (1, 0):
+            k = L.fa_debug_local_fwd_plan(*shape, al, al, nws, 256, lf)
+            assert k == L.fa_debug_dense_fwd_plan(*shape, 2, 0, 2, al, al, nws, 256, df) and k >= 0
+            # local out: local, causal bits, pad, ldk, nsplit, rows, grid, total
+            assert list(lf) == [1, df[0], df[1], df[2], df[3], df[5], df[8], df[16]] and df[0] == 0
+            k = L.fa_debug_local_bwd_plan(*shape, al, nws, 256, lb)
+            assert k == L.fa_debug_dense_bwd_plan(*shape, 2, 0, 0, 3, -1, al, nws, 256, db) and k >= 0
+            # local out: padded, N, Nk, d, dv as run, total
+            assert list(lb) == list(db)[:5] + [db[24]]
+    # the mask is a value, not a flag: anything else is an invalid argument, and 2 needs Nk >= N
+    assert L.fa_debug_dense_fwd_plan(1, 64, 64, 64, 64, 1, 3, 0, 2, 1, 1, 0, 256, df) == -1
+    assert L.fa_debug_dense_bwd_plan(1, 64, 64, 64, 64, 1, -1, 0, 0, 3, -1, 1, 0, 256, db) == -1
+    assert L.fa_debug_dense_fwd_plan(1, 64, 63, 64, 64, 1, 2, 0, 2, 1, 1, 0, 256, df) == -1
 
 
 # ---- the Python mirror ---------------------------------------------------------------

@@ -7,7 +7,7 @@
 
 Every function of old.s is looked up in new.s by its mangled name (a trailing defaulted
 `false` template argument, Lb0E, is dropped, so a kernel that gained `bool CAUSAL = false`
-still matches) and its body (the lines between its label and its .Lfunc_end, with the function's
+still matches, and the dense family's mask argument is reduced to one spelling: key()) and its body (the lines between its label and its .Lfunc_end, with the function's
 own mangled name and the compiler's local label numbers normalised) is compared.  Prints one
 line per function that differs or is missing and a final count; exit status 1 if any differs.
 """
@@ -38,7 +38,20 @@ def functions(path: str) -> dict:
 
 
 def key(mangled: str) -> str:
-    return re.sub(r"(Lb0E)+(?=EEv)", "", mangled)
+    """The mangled name with its dense-family mask argument in one canonical spelling: nothing
+    for no mask, @M1 causal, @M2 local.  Reduces to it the old trailing `bool CAUSAL, bool LOCAL`
+    pair (defaults are mangled too), the new trailing `DenseMask MASK`, and the old forward
+    wrapper names causal_fwd_* / local_fwd_* (now dense_fwd_*<..., MASK>)."""
+    k = re.sub(r"LNS_9DenseMaskE([012])E(?=EEv)", lambda m: "@M" + m.group(1), mangled)
+    k = re.sub(r"Lb([01])ELb([01])E(?=EEv)",
+               lambda m: {"00": "@M0", "10": "@M1", "01": "@M2"}.get(m.group(1) + m.group(2), m.group(0)), k)
+    m = re.match(r"(_ZN2fa)(\d+)(causal|local)(_fwd_\w+)$", k)
+    if m and int(m.group(2)) < len(m.group(3) + m.group(4)):
+        n = int(m.group(2)) - len(m.group(3))              # the name's characters after the mask's word
+        rest = m.group(4)
+        k = "%s%ddense%s" % (m.group(1), n + 5, rest[:n]) + re.sub(r"(?=EEv)", "@M1" if m.group(3) == "causal" else "@M2", rest[n:], count=1)
+    k = k.replace("@M0", "")
+    return re.sub(r"(Lb0E)+(?=EEv)", "", k)
 
 
 def norm(body, own: str):
