@@ -14,6 +14,7 @@
 #include <string>
 
 #include "../../include/fa_hip.h"
+#include "fa_circulant_plan.h"   // the circulant plans (host functions)
 #include "fa_dense_plan.h"   // the dense plans (host functions)
 #include "fa_internal.h"
 #include "fa_windowed.h"   // the windowed plans (host functions; no kernel is instantiated here)
@@ -224,6 +225,40 @@ int fa_debug_last_circ_fwd_kernel(void) { return fa::g_circ_fwd_last_kernel; }
 // Not part of the public header: which kernel family the calling thread's last
 // fa_circulant_bwd launched: 0 none, 1 MFMA tiled, 2 SIMT, 3 Float64 (tests).
 int fa_debug_last_circ_bwd_kernel(void) { return fa::g_circ_bwd_last_kernel; }
+
+// Not part of the public header (tests): the plan of a circulant forward / backward,
+// fa::circ_fwd_plan / fa::circ_bwd_plan (fa_circulant_plan.h).  Returns the kernel, a
+// fa::CircFwdKernel (the codes of fa_debug_last_circ_fwd_kernel), or the family, a
+// fa::CircBwdFamily (those of fa_debug_last_circ_bwd_kernel); -1 for invalid arguments (out
+// is left alone) and for a shape the launcher refuses.  Writes the plan's other fields to out
+// (may be null).  Every input is an argument, the knob (a fa_debug_set_circ_generic value) and
+// the 16-B alignment facts included: nothing is read from the thread's knobs or the device.
+// forward out[9]: Dc, DVc, simt_class, simt_kt, nqb, total_wg, grid, block, status.
+int fa_debug_circ_fwd_plan(int dtype, int64_t N, int64_t d, int64_t dv, int64_t batch, int64_t W, int knob,
+                           int kv_aligned16, int64_t* out) {
+    if (!valid_dtype(dtype) || N < 1 || d < 1 || dv < 1 || batch < 1 || W < 1) return -1;
+    const fa::CircFwdPlan pl = fa::circ_fwd_plan(dtype, N, d, dv, batch, W, knob, kv_aligned16 != 0);
+    if (out) {
+        const int64_t f[9] = {pl.Dc, pl.DVc, pl.simt_class, pl.simt_kt, pl.nqb, pl.total_wg, pl.grid, pl.block, pl.status};
+        for (int i = 0; i < 9; ++i) out[i] = f[i];
+    }
+    return pl.kernel;
+}
+// backward out[15]: w1, w1_grid, prepass_vec, prepass_grid, Dc, DVc, nblk, total_wg, grid, lds_dq,
+// lds_dkdv, off_nD, off_nlse, total, status.
+int fa_debug_circ_bwd_plan(int dtype, int64_t N, int64_t d, int64_t dv, int64_t batch, int64_t W, int knob,
+                           int qkv_aligned16, int o_aligned16, int do_aligned16, int64_t* out) {
+    if (!valid_dtype(dtype) || N < 1 || d < 1 || dv < 1 || batch < 1 || W < 1) return -1;
+    const fa::CircBwdPlan pl = fa::circ_bwd_plan(dtype, N, d, dv, batch, W, knob, qkv_aligned16 != 0, o_aligned16 != 0,
+                                                 do_aligned16 != 0);
+    if (out) {
+        const int64_t f[15] = {pl.w1, pl.w1_grid, pl.prepass_vec, pl.prepass_grid, pl.Dc, pl.DVc, pl.nblk, pl.total_wg,
+                               pl.grid, (int64_t)pl.lds_dq, (int64_t)pl.lds_dkdv, (int64_t)pl.off_nD,
+                               (int64_t)pl.off_nlse, (int64_t)pl.total, pl.status};
+        for (int i = 0; i < 15; ++i) out[i] = f[i];
+    }
+    return pl.family;
+}
 
 // Not part of the public header: windowed forward path override (1 composed,
 // 2 register-gather fused, 3 one-window row-shift (ws <= 7) / row-scatter, 4 four-window
@@ -657,26 +692,38 @@ int fa_windowed_bwd(int dtype, const void* q, const void* k, const void* v, cons
     return rc == FA_OK ? ok() : fail(rc, fn, why);
 }
 
+// The checks fa_circulant_fwd and fa_circulant_bwd share, in their order.  True when the call
+// is complete, with its status in *rc: an argument refused, or an empty input (circulant_fa!
+// loops over no row / slab; no query, no key: no gradient element), which dereferences
+// nothing, so the null-pointer check (null_ptr: one of the call's tensors is null) comes after.
+static bool circ_call_done(const char* fn, int dtype, int64_t N, int64_t d, int64_t dv, int64_t batch, int64_t W,
+                           bool null_ptr, int* rc) {
+    if (!valid_dtype(dtype)) *rc = fail(FA_ERR_INVALID_ARG, fn, "unknown dtype");
+    else if (N < 0 || d < 1 || dv < 1 || batch < 0)
+        *rc = fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: d, dv must be >= 1, N, batch >= 0");
+    else if (W < 1) *rc = fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: window size W must be >= 1");
+    else if (N == 0 || batch == 0) *rc = ok();
+    else if (null_ptr) *rc = fail(FA_ERR_INVALID_ARG, fn, "null pointer");
+    else return false;
+    return true;
+}
+
 int fa_circulant_fwd(int dtype, const void* Q, const void* K, const void* V, void* O, float* l, float* m,
                      int64_t N, int64_t d, int64_t dv, int64_t batch, int64_t W, float scale,
                      void* hip_stream) {
     static const char* fn = "fa_circulant_fwd";
-    if (!valid_dtype(dtype)) return fail(FA_ERR_INVALID_ARG, fn, "unknown dtype");
-    if (N < 0 || d < 1 || dv < 1 || batch < 0)
-        return fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: d, dv must be >= 1, N, batch >= 0");
-    if (W < 1) return fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: window size W must be >= 1");
-    if (N == 0 || batch == 0) return ok();   // circulant_fa! loops over no row / slab
-    if (!Q || !K || !V || !O || !l || !m) return fail(FA_ERR_INVALID_ARG, fn, "null pointer");
+    int rc;
+    if (circ_call_done(fn, dtype, N, d, dv, batch, W, !Q || !K || !V || !O || !l || !m, &rc)) return rc;
     fa::CircArgs a{dtype, Q, K, V, O, l, m, N, d, dv, batch, W, resolve_scale(scale, d)};
     a.scale64 = resolve_scale64(scale, d);
     const char* why = "";
-    const int rc = fa::launch_circulant_fwd(a, (hipStream_t)hip_stream, &why);
+    rc = fa::launch_circulant_fwd(a, (hipStream_t)hip_stream, &why);
     return rc == FA_OK ? ok() : fail(rc, fn, why);
 }
 
 size_t fa_circulant_bwd_workspace(int dtype, int64_t N, int64_t d, int64_t dv, int64_t batch, int64_t W) {
     if (!valid_dtype(dtype) || N < 1 || d < 1 || dv < 1 || batch < 1 || W < 1) return 0;
-    return fa::circulant_bwd_workspace(dtype, N, batch);
+    return fa::circulant_bwd_workspace(dtype, N, d, dv, batch, W);
 }
 
 int fa_circulant_bwd(int dtype, const void* Q, const void* K, const void* V, const void* O, const void* dO,
@@ -684,18 +731,14 @@ int fa_circulant_bwd(int dtype, const void* Q, const void* K, const void* V, con
                      int64_t dv, int64_t batch, int64_t W, float scale, void* workspace,
                      size_t workspace_bytes, void* hip_stream) {
     static const char* fn = "fa_circulant_bwd";
-    if (!valid_dtype(dtype)) return fail(FA_ERR_INVALID_ARG, fn, "unknown dtype");
-    if (N < 0 || d < 1 || dv < 1 || batch < 0)
-        return fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: d, dv must be >= 1, N, batch >= 0");
-    if (W < 1) return fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: window size W must be >= 1");
-    if (N == 0 || batch == 0) return ok();   // no query, no key: no gradient element
-    if (!Q || !K || !V || !O || !dO || !l || !m || !dQ || !dK || !dV)
-        return fail(FA_ERR_INVALID_ARG, fn, "null pointer");
+    int rc;
+    if (circ_call_done(fn, dtype, N, d, dv, batch, W, !Q || !K || !V || !O || !dO || !l || !m || !dQ || !dK || !dV, &rc))
+        return rc;
     fa::CircBwdArgs a{dtype, Q, K, V, O, dO, l, m, dQ, dK, dV, N, d, dv, batch, W,
                       resolve_scale(scale, d), workspace, workspace_bytes};
     a.scale64 = resolve_scale64(scale, d);
     const char* why = "";
-    const int rc = fa::launch_circulant_bwd(a, (hipStream_t)hip_stream, &why);
+    rc = fa::launch_circulant_bwd(a, (hipStream_t)hip_stream, &why);
     return rc == FA_OK ? ok() : fail(rc, fn, why);
 }
 

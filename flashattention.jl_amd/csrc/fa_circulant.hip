@@ -27,8 +27,7 @@
 //    query, LDS-tiled key union, exact fp32 arithmetic (below).
 //  * circ_fwd_generic: one wave per query, lanes over features — kept only as a
 //    reference path behind fa_debug_set_circ_generic.
-#include <type_traits>
-
+#include "fa_circulant_plan.h"
 #include "fa_common.h"
 #include "fa_internal.h"
 #include "../../include/fa_hip.h"
@@ -468,86 +467,51 @@ __global__ __launch_bounds__(256, 2) void circ_fwd_tiled(CircParams P) {
 }
 
 // --------------------------------------------------------------------------
-// launcher
+// launcher: circ_fwd_plan (fa_circulant_plan.h) names the kernel, its classes and its grid;
+// nothing below decides any of them again
 // --------------------------------------------------------------------------
-static bool circ_aligned16(const void* ptr) { return ((uintptr_t)ptr & 15u) == 0; }
-
-template <class T, int D>
-static void launch_circ_tiled(const CircParams& p, int DVc, hipStream_t s) {
-    const dim3 grid((unsigned)p.total_wg), blk(256);
-    switch (DVc) {
-        case 32: hipLaunchKernelGGL((circ_fwd_tiled<T, D, 32>), grid, blk, 0, s, p); break;
-        case 64: hipLaunchKernelGGL((circ_fwd_tiled<T, D, 64>), grid, blk, 0, s, p); break;
-        default: hipLaunchKernelGGL((circ_fwd_tiled<T, D, 128>), grid, blk, 0, s, p); break;
-    }
-}
-
 template <class T>
-static void launch_circ_typed(CircParams p, int64_t batch, bool fast, hipStream_t s) {
-    if constexpr (!std::is_same<T, float>::value) {
-        if (fast) {
-            const int Dc = head_dim_class(p.d), DVc = head_dim_class(p.dv);
-            p.nqb = (p.N + 127) / 128;
-            p.total_wg = (int)(p.nqb * batch);
-            g_circ_fwd_last_kernel = 1;
-            switch (Dc) {
-                case 32: launch_circ_tiled<T, 32>(p, DVc, s); break;
-                case 64: launch_circ_tiled<T, 64>(p, DVc, s); break;
-                default: launch_circ_tiled<T, 128>(p, DVc, s); break;
-            }
-            return;
-        }
+static void launch_circ_typed(const CircFwdPlan& pl, const CircParams& p, hipStream_t s) {
+    const dim3 grid((unsigned)pl.grid), blk(pl.block);
+    switch (pl.kernel) {
+        case kCircFwdTiled:
+            if constexpr (sizeof(T) == 2)   // (never planned for fp32)
+                by_dim_class(pl.Dc, [&](auto D) {
+                    by_dim_class(pl.DVc, [&](auto DV) {
+                        hipLaunchKernelGGL((circ_fwd_tiled<T, decltype(D)::value, decltype(DV)::value>), grid, blk, 0, s, p);
+                    });
+                });
+            break;
+        case kCircFwdWave: hipLaunchKernelGGL((circ_fwd_generic<T>), grid, blk, 0, s, p); break;
+        default:   // kCircFwdSimt
+            by_dim_class(pl.simt_class, [&](auto C) {
+                constexpr int c = decltype(C)::value;
+                hipLaunchKernelGGL((circ_fwd_simt<T, c, c, circ_simt_kt(c)>), grid, blk, 0, s, p);
+            });
     }
-    // small grids (< 128 workgroups of 256 queries) keep one wave per query: more
-    // parallelism there (N 4096, d 32, one slab, W 129 fp32: 72 vs 137 us)
-    if (g_circ_force_generic == 1 || (g_circ_force_generic != 2 && (int64_t)(p.N + 255) / 256 * batch < 128)) {
-        p.total_wg = (int)batch;   // one-wave-per-query kernel: slab count
-        const int64_t waves = (int64_t)p.N * batch;
-        g_circ_fwd_last_kernel = 2;
-        hipLaunchKernelGGL((circ_fwd_generic<T>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, p);
-        return;
-    }
-    g_circ_fwd_last_kernel = 3;
-    p.total_wg = (int)((p.N + 255) / 256 * batch);
-    const dim3 grid((unsigned)p.total_wg);
-    const int Dc = head_dim_class(p.d), DVc = head_dim_class(p.dv);
-#define FA_CS(DD, DVV, KTT) hipLaunchKernelGGL((circ_fwd_simt<T, DD, DVV, KTT>), grid, dim3(256), 0, s, p)
-    if (Dc <= 32 && DVc <= 32) FA_CS(32, 32, 32);
-    else if (Dc <= 64 && DVc <= 64) FA_CS(64, 64, 32);
-    else FA_CS(128, 128, 8);
-#undef FA_CS
 }
 
 int launch_circulant_fwd(const CircArgs& a, hipStream_t s, const char** why) {
-    if (!head_dim_class(a.d) || !head_dim_class(a.dv)) {
-        *why = "head dimension exceeds the compiled maximum (128)";
-        return FA_ERR_UNSUPPORTED;
-    }
-    const int64_t esz = (int64_t)dtype_size(a.dtype);
-    if (a.N * a.d * esz >= (int64_t)INT32_MAX || a.N * a.dv * esz >= (int64_t)INT32_MAX ||
-        a.W > INT32_MAX / 2 || a.N * a.batch > (int64_t)INT32_MAX * 2) {
-        *why = "per-slab extent or band width exceeds the 32-bit addressing of the kernels";
-        return FA_ERR_UNSUPPORTED;
+    const CircFwdPlan pl = circ_fwd_plan(a.dtype, a.N, a.d, a.dv, a.batch, a.W, g_circ_force_generic,
+                                         aligned16(a.K) && aligned16(a.V));
+    if (pl.kernel == kCircFwdNone) {
+        *why = pl.why;
+        return pl.status;
     }
     CircParams p;
     p.Q = a.Q; p.K = a.K; p.V = a.V; p.O = a.O; p.l = a.l; p.m = a.m;
     p.N = (int)a.N; p.d = (int)a.d; p.dv = (int)a.dv; p.W = (int)a.W; p.p = (int)((a.W - 1) / 2);
-    p.nqb = 0; p.total_wg = 0;
+    p.nqb = (int)pl.nqb; p.total_wg = (int)pl.total_wg;
     p.scale = a.scale;
     p.scale_log2 = a.scale * kLog2e;
-    const bool fast = (a.dtype == FA_DTYPE_BF16 || a.dtype == FA_DTYPE_F16) && a.N % 8 == 0 && circ_aligned16(a.K) && circ_aligned16(a.V) &&
-                      ((a.N + 127) / 128) * a.batch <= INT32_MAX && g_circ_force_generic == 0;
     switch (a.dtype) {
-        case FA_DTYPE_BF16: launch_circ_typed<bf16>(p, a.batch, fast, s); break;
-        case FA_DTYPE_F16: launch_circ_typed<f16>(p, a.batch, fast, s); break;
-        case FA_DTYPE_F32: launch_circ_typed<float>(p, a.batch, false, s); break;
-        case FA_DTYPE_F64: {
-            const int64_t waves = a.N * a.batch;
-            g_circ_fwd_last_kernel = 4;
-            hipLaunchKernelGGL(circ_fwd_f64, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, p,
+        case FA_DTYPE_BF16: launch_circ_typed<bf16>(pl, p, s); break;
+        case FA_DTYPE_F16: launch_circ_typed<f16>(pl, p, s); break;
+        case FA_DTYPE_F32: launch_circ_typed<float>(pl, p, s); break;
+        case FA_DTYPE_F64:
+            hipLaunchKernelGGL(circ_fwd_f64, dim3((unsigned)pl.grid), dim3(pl.block), 0, s, p,
                                a.scale64 > 0.0 ? a.scale64 : (double)a.scale, a.batch);
             break;
-        }
         default: *why = "unknown dtype"; return FA_ERR_INVALID_ARG;
     }
     const hipError_t e = hipGetLastError();
@@ -555,6 +519,7 @@ int launch_circulant_fwd(const CircArgs& a, hipStream_t s, const char** why) {
         *why = hipGetErrorString(e);
         return FA_ERR_HIP;
     }
+    g_circ_fwd_last_kernel = pl.kernel;
     return FA_OK;
 }
 

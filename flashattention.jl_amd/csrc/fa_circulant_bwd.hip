@@ -29,9 +29,8 @@
 //  * circ_bwd_dq_simt / circ_bwd_dkdv_simt (every dtype, any N / alignment): 32 x 32
 //    tiles in LDS, arithmetic in A = float (exact fp32 dot products) or, for Float64,
 //    double with the row statistics recomputed in double by the pre-pass.
-#include <type_traits>
-
 #include "fa_bwd_common.h"
+#include "fa_circulant_plan.h"
 #include "fa_internal.h"
 #include "../../include/fa_hip.h"
 
@@ -624,126 +623,71 @@ __global__ __launch_bounds__(256, (D + DV > 128) ? 1 : 2) void circ_bwd_dkdv_til
 }
 
 // --------------------------------------------------------------------------
-// launcher
+// launcher: circ_bwd_plan (fa_circulant_plan.h) names the kernels, their grids and LDS sizes
+// and the workspace layout; nothing below decides any of them again
 // --------------------------------------------------------------------------
-static bool cb_aligned16(const void* ptr) { return ((uintptr_t)ptr & 15u) == 0; }
-static size_t cb_al256(size_t x) { return (x + 255) & ~(size_t)255; }
+static_assert(kCT == kCircBwdSimtTile && kCThreads == kCircBwdThreads, "the plan's constants");
 
-size_t circulant_bwd_workspace(int dtype, int64_t N, int64_t batch) {
-    const size_t asz = dtype == FA_DTYPE_F64 ? 8 : 4;
-    return 256 + 2 * cb_al256((size_t)N * (size_t)batch * asz);
+size_t circulant_bwd_workspace(int dtype, int64_t N, int64_t d, int64_t dv, int64_t batch, int64_t W) {
+    return circ_bwd_plan(dtype, N, d, dv, batch, W, kCircAuto, true, true, true).total;
 }
 
-template <class T, int D>
-static void launch_cb_tiled(const CircBwdParams& p, int DVc, hipStream_t s) {
-    const dim3 grid((unsigned)p.total_wg), blk(256);
-#define FA_CB(DVV)                                                                    \
-    hipLaunchKernelGGL((circ_bwd_dq_tiled<T, D, DVV>), grid, blk, 0, s, p);           \
-    hipLaunchKernelGGL((circ_bwd_dkdv_tiled<T, D, DVV>), grid, blk, 0, s, p)
-    switch (DVc) {
-        case 32: FA_CB(32); break;
-        case 64: FA_CB(64); break;
-        default: FA_CB(128); break;
-    }
-#undef FA_CB
-}
-
+// T: the tensors' element type; A: the SIMT kernels' arithmetic (double for Float64)
 template <class T, class A>
-static void launch_cb_simt(const CircBwdParams& p, hipStream_t s) {
-    const int64_t nt = ((int64_t)p.N + kCT - 1) / kCT * p.batch;
-    const size_t rows = kCT * (2 * (p.d + 1) + 2 * (p.dv + 1));
-    const size_t sm_dq = sizeof(A) * (rows + kCT * (kCT + 1));
-    const size_t sm_kv = sizeof(A) * (rows + 2 * kCT * (kCT + 1) + 2 * kCT);
+static void launch_cb_typed(const CircBwdPlan& pl, const CircBwdParams& p, hipStream_t s) {
+    const dim3 grid((unsigned)pl.grid), blk(kCircBwdThreads);
+    if (pl.w1) {
+        const int64_t total = (int64_t)p.N * p.batch;
+        hipLaunchKernelGGL(circ_bwd_w1<T>, dim3((unsigned)pl.w1_grid), blk, 0, s, p, total * p.d, total * p.dv);
+        return;
+    }
+    if constexpr (sizeof(T) == 2) {
+        if (pl.prepass_vec) hipLaunchKernelGGL(circ_bwd_prepass_v<T>, dim3((unsigned)pl.prepass_grid), blk, 0, s, p);
+    }
+    if (!pl.prepass_vec) hipLaunchKernelGGL((circ_bwd_prepass<T, A>), dim3((unsigned)pl.prepass_grid), blk, 0, s, p);
+    if (pl.family == kCircBwdMfma) {
+        if constexpr (sizeof(T) == 2)   // (never planned for fp32, Float64)
+            by_dim_class(pl.Dc, [&](auto D) {
+                by_dim_class(pl.DVc, [&](auto DV) {
+                    hipLaunchKernelGGL((circ_bwd_dq_tiled<T, decltype(D)::value, decltype(DV)::value>), grid, blk, 0, s, p);
+                    hipLaunchKernelGGL((circ_bwd_dkdv_tiled<T, decltype(D)::value, decltype(DV)::value>), grid, blk, 0, s, p);
+                });
+            });
+        return;
+    }
     // > 64 KiB of dynamic LDS at d = dv = 128 (gfx950 has 160 KiB per CU)
-    (void)hipFuncSetAttribute((const void*)circ_bwd_dq_simt<T, A>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_dq);
-    (void)hipFuncSetAttribute((const void*)circ_bwd_dkdv_simt<T, A>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_kv);
-    hipLaunchKernelGGL((circ_bwd_dq_simt<T, A>), dim3((unsigned)nt), dim3(kCThreads), sm_dq, s, p);
-    hipLaunchKernelGGL((circ_bwd_dkdv_simt<T, A>), dim3((unsigned)nt), dim3(kCThreads), sm_kv, s, p);
-}
-
-template <class T>
-static void launch_cb_w1(const CircBwdParams& p, hipStream_t s) {
-    const int64_t total = (int64_t)p.N * p.batch;
-    const int64_t nqk = total * p.d, nv = total * p.dv;
-    const int64_t blocks = ((nqk > nv ? nqk : nv) + 255) / 256;
-    hipLaunchKernelGGL(circ_bwd_w1<T>, dim3((unsigned)(blocks < (1 << 20) ? blocks : (1 << 20))), dim3(256), 0, s, p, nqk, nv);
-}
-
-template <class T>
-static int launch_cb_typed(CircBwdParams p, bool fast, hipStream_t s) {
-    const int64_t total = (int64_t)p.N * p.batch;
-    if (p.W == 1) {
-        launch_cb_w1<T>(p, s);
-        return 2;
-    }
-    bool vec = false;
-    if constexpr (sizeof(T) == 2) {
-        vec = p.N % 8 == 0 && cb_aligned16(p.O) && cb_aligned16(p.dO);
-        if (vec) hipLaunchKernelGGL(circ_bwd_prepass_v<T>, dim3((unsigned)((total / 8 + 255) / 256)), dim3(256), 0, s, p);
-    }
-    if (!vec) hipLaunchKernelGGL((circ_bwd_prepass<T, float>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p);
-    if constexpr (sizeof(T) == 2) {
-        if (fast) {
-            p.nblk = (p.N + 127) / 128;
-            p.total_wg = (int)(p.nblk * p.batch);
-            switch (head_dim_class(p.d)) {
-                case 32: launch_cb_tiled<T, 32>(p, head_dim_class(p.dv), s); break;
-                case 64: launch_cb_tiled<T, 64>(p, head_dim_class(p.dv), s); break;
-                default: launch_cb_tiled<T, 128>(p, head_dim_class(p.dv), s); break;
-            }
-            return 1;
-        }
-    }
-    launch_cb_simt<T, float>(p, s);
-    return 2;
+    (void)hipFuncSetAttribute((const void*)circ_bwd_dq_simt<T, A>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_dq);
+    (void)hipFuncSetAttribute((const void*)circ_bwd_dkdv_simt<T, A>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_dkdv);
+    hipLaunchKernelGGL((circ_bwd_dq_simt<T, A>), grid, blk, pl.lds_dq, s, p);
+    hipLaunchKernelGGL((circ_bwd_dkdv_simt<T, A>), grid, blk, pl.lds_dkdv, s, p);
 }
 
 int launch_circulant_bwd(const CircBwdArgs& a, hipStream_t s, const char** why) {
-    if (!head_dim_class(a.d) || !head_dim_class(a.dv)) {
-        *why = "head dimension exceeds the compiled maximum (128)";
-        return FA_ERR_UNSUPPORTED;
+    const CircBwdPlan pl = circ_bwd_plan(a.dtype, a.N, a.d, a.dv, a.batch, a.W, g_circ_force_generic,
+                                         aligned16(a.Q) && aligned16(a.K) && aligned16(a.V), aligned16(a.O), aligned16(a.dO));
+    if (pl.family == kCircBwdNone) {
+        *why = pl.why;
+        return pl.status;
     }
-    const int64_t esz = (int64_t)dtype_size(a.dtype);
-    if (a.N * a.d * esz >= (int64_t)INT32_MAX || a.N * a.dv * esz >= (int64_t)INT32_MAX ||
-        a.W > INT32_MAX / 2 || a.N * a.batch > (int64_t)INT32_MAX * 2) {
-        *why = "per-slab extent or band width exceeds the 32-bit addressing of the kernels";
-        return FA_ERR_UNSUPPORTED;
-    }
-    const size_t asz = a.dtype == FA_DTYPE_F64 ? 8 : 4;
-    const size_t part = cb_al256((size_t)a.N * (size_t)a.batch * asz);
-    if (!a.workspace || a.workspace_bytes < circulant_bwd_workspace(a.dtype, a.N, a.batch)) {
+    if (!a.workspace || a.workspace_bytes < pl.total) {
         *why = "workspace missing or smaller than fa_circulant_bwd_workspace()";
         return FA_ERR_WORKSPACE;
     }
-    char* const w = (char*)(((uintptr_t)a.workspace + 255) & ~(uintptr_t)255);
+    char* const w = al256(a.workspace);
     CircBwdParams p;
     p.Q = a.Q; p.K = a.K; p.V = a.V; p.O = a.O; p.dO = a.dO; p.l = a.l; p.m = a.m;
     p.dQ = a.dQ; p.dK = a.dK; p.dV = a.dV;
-    p.nD = w; p.nlse = w + part;
+    p.nD = w + pl.off_nD; p.nlse = w + pl.off_nlse;
     p.N = (int)a.N; p.d = (int)a.d; p.dv = (int)a.dv; p.W = (int)a.W; p.p = (int)((a.W - 1) / 2);
-    p.nblk = 0; p.total_wg = 0; p.batch = a.batch;
+    p.nblk = (int)pl.nblk; p.total_wg = (int)pl.total_wg; p.batch = a.batch;
     p.scale = a.scale;
     p.scale_log2 = a.scale * kLog2e;
     p.scale64 = a.scale64 > 0.0 ? a.scale64 : (double)a.scale;
-    const bool fast = (a.dtype == FA_DTYPE_BF16 || a.dtype == FA_DTYPE_F16) && a.N % 8 == 0 &&
-                      cb_aligned16(a.Q) && cb_aligned16(a.K) && cb_aligned16(a.V) && cb_aligned16(a.dO) &&
-                      ((a.N + 127) / 128) * a.batch <= INT32_MAX && g_circ_force_generic == 0;
-    int kind = 0;
     switch (a.dtype) {
-        case FA_DTYPE_BF16: kind = launch_cb_typed<bf16>(p, fast, s); break;
-        case FA_DTYPE_F16: kind = launch_cb_typed<f16>(p, fast, s); break;
-        case FA_DTYPE_F32: kind = launch_cb_typed<float>(p, false, s); break;
-        case FA_DTYPE_F64: {
-            kind = 3;
-            if (a.W == 1) {
-                launch_cb_w1<double>(p, s);
-                break;
-            }
-            const int64_t total = a.N * a.batch;
-            hipLaunchKernelGGL((circ_bwd_prepass<double, double>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p);
-            launch_cb_simt<double, double>(p, s);
-            break;
-        }
+        case FA_DTYPE_BF16: launch_cb_typed<bf16, float>(pl, p, s); break;
+        case FA_DTYPE_F16: launch_cb_typed<f16, float>(pl, p, s); break;
+        case FA_DTYPE_F32: launch_cb_typed<float, float>(pl, p, s); break;
+        case FA_DTYPE_F64: launch_cb_typed<double, double>(pl, p, s); break;
         default: *why = "unknown dtype"; return FA_ERR_INVALID_ARG;
     }
     const hipError_t e = hipGetLastError();
@@ -751,7 +695,7 @@ int launch_circulant_bwd(const CircBwdArgs& a, hipStream_t s, const char** why) 
         *why = hipGetErrorString(e);
         return FA_ERR_HIP;
     }
-    g_circ_bwd_last_kernel = kind;
+    g_circ_bwd_last_kernel = pl.family;
     return FA_OK;
 }
 

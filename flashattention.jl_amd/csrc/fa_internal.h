@@ -150,10 +150,14 @@ size_t windowed_workspace(int dtype, const WindowGeom& g, int64_t d, int64_t dv,
 size_t windowed_fwd_workspace(int dtype, const WindowGeom& g, int64_t d, int64_t dv, int64_t batch);
 int launch_windowed_fwd(const WindowedArgs& a, hipStream_t s, const char** why);
 int launch_windowed_bwd(const WindowedBwdArgs& a, hipStream_t s, const char** why);
+// circulant attention (fa_circulant.hip, fa_circulant_bwd.hip): each launcher asks its plan
+// (fa_circulant_plan.h: circ_fwd_plan, circ_bwd_plan) once, with the thread's circulant
+// knob and the tensors' 16-B alignment facts, refuses with the plan's status
+// and message (head dims, then the 32-bit extents), and launches what the plan names.  The
+// backward then checks the workspace against the plan's total, which is what
+// circulant_bwd_workspace returns for the shape, before the first launch.
 int launch_circulant_fwd(const CircArgs& a, hipStream_t s, const char** why);
-// circulant backward (fa_circulant_bwd.hip): checks the head dims, the 32-bit extents and
-// the workspace, in that order, before the first launch
-size_t circulant_bwd_workspace(int dtype, int64_t N, int64_t batch);
+size_t circulant_bwd_workspace(int dtype, int64_t N, int64_t d, int64_t dv, int64_t batch, int64_t W);
 int launch_circulant_bwd(const CircBwdArgs& a, hipStream_t s, const char** why);
 // window (unfold) / unwindow (fold, sum over overlaps) of one tensor (S..., C, B) <-> (T, C, L, B)
 int launch_window(int dtype, const void* src, void* dst, const WindowGeom& g, int64_t C, int64_t batch,
@@ -250,7 +254,7 @@ extern thread_local int g_bwd_nodirect;       // single pass (tests): chain-B ta
 extern thread_local int g_bwd_xcd;            // single pass: one XCD per slab where eligible (-1 auto, 0 never)
 extern thread_local int g_win_force_composed; // windowed: forced path (a WinMode, fa_windowed.h)
 extern thread_local int g_win_bwd_grid;       // windowed: strip backward workgroups (0: one per CU)
-extern thread_local int g_circ_force_generic; // circulant: forced kernel
+extern thread_local int g_circ_force_generic; // circulant: forced kernel (a CircKnob, fa_circulant_plan.h)
 extern thread_local int g_circ_fwd_last_kernel; // circulant forward: kernel of the last launch (1 tiled MFMA, 2 one wave per query, 3 LDS-tiled SIMT, 4 Float64)
 extern thread_local int g_circ_bwd_last_kernel; // circulant backward: family of the last launch (1 MFMA, 2 SIMT, 3 Float64)
 

@@ -158,6 +158,36 @@ def test_circulant_simt_vs_reference_kernel(fa, N, d, dv, W, dtype):
     assert_close(_np(o1), _np(o2), dtype, "O simt vs one-wave")
 
 
+def test_plan_is_what_ran(fa):
+    """The kernel the launcher reports is circ_fwd_plan's answer (fa_debug_circ_fwd_plan) for the
+    shape, the knob in force and K's and V's actual 16-B alignment, on the smallest shapes that
+    reach every branch: tiled MFMA, one wave per query (ragged N; fp32), the SIMT kernel under
+    knob 2, Float64."""
+    import ctypes
+    L = fa.lib()
+    i64, ci = ctypes.c_int64, ctypes.c_int
+    L.fa_debug_circ_fwd_plan.restype = ci
+    L.fa_debug_circ_fwd_plan.argtypes = [ci] + [i64] * 5 + [ci] * 2 + [ctypes.POINTER(i64)]
+    d, dv, W, B = 32, 32, 9, 2
+    rng = np.random.default_rng(11)
+    ran = []
+    for tdt, N, knob in ((torch.bfloat16, 256, 0), (torch.bfloat16, 250, 0), (torch.bfloat16, 250, 2),
+                         (torch.float32, 256, 0), (torch.float64, 64, 0)):
+        Q, K, V = (fa.jl_tensor(rng.standard_normal((N, c, B)), tdt) for c in (d, d, dv))
+        old = L.fa_debug_set_circ_generic(knob)
+        try:
+            fa.circulant_fa(Q, K, V, W)
+            got = L.fa_debug_last_circ_fwd_kernel()
+        finally:
+            L.fa_debug_set_circ_generic(old)
+        kv = int(K.data_ptr() % 16 == 0 and V.data_ptr() % 16 == 0)
+        want = L.fa_debug_circ_fwd_plan(fa.DTYPES[tdt], N, d, dv, B, W, knob, kv, None)
+        assert got == want, (tdt, N, knob, got, want)
+        ran.append(want)
+    torch.cuda.synchronize()
+    assert ran == [1, 2, 3, 2, 4]   # tiled MFMA, one wave per query, LDS-tiled SIMT, (fp32: 2 blocks) one wave, Float64
+
+
 @pytest.mark.parametrize("dtype", list(DT))
 @pytest.mark.parametrize("N,d,dv,W,B", [(96, 32, 16, 7, 2), (200, 64, 64, 65, 1), (50, 16, 8, 64, 2)])
 def test_circulant_dpa_vs_oracle(fa, dtype, N, d, dv, W, B):

@@ -156,6 +156,31 @@ def test_kernel_family_proof(fa):
     assert device_run(fa, *shape, BF)["kind"] == MFMA   # the knob was restored
 
 
+def test_plan_is_what_ran(fa):
+    """The family the launcher reports is circ_bwd_plan's answer (fa_debug_circ_bwd_plan) for the
+    shape, the knob in force and the tensors' actual 16-B alignment, on the smallest shapes that
+    reach every branch: MFMA, SIMT by ragged N, by the knob and by fp32, Float64, and W = 1."""
+    L = fa.lib()
+    i64, ci = ctypes.c_int64, ctypes.c_int
+    L.fa_debug_circ_bwd_plan.restype = ci
+    L.fa_debug_circ_bwd_plan.argtypes = [ci] + [i64] * 5 + [ci] * 4 + [ctypes.POINTER(i64)]
+    d, dv, B = 32, 32, 2
+    ran = []
+    for dtype, N, W, knob in ((BF, 256, 9, 0), (BF, 250, 9, 0), (BF, 256, 9, 2), (F32, 256, 9, 0), (F64T, 64, 9, 0),
+                              (BF, 256, 1, 0), (F64T, 64, 1, 0)):
+        old = L.fa_debug_set_circ_generic(knob)
+        try:
+            r = device_run(fa, N, d, dv, W, B, dtype)
+        finally:
+            L.fa_debug_set_circ_generic(old)
+        al = lambda *names: int(all(r[n].data_ptr() % 16 == 0 for n in names))
+        out = (i64 * 15)()
+        want = L.fa_debug_circ_bwd_plan(fa.DTYPES[DT[dtype]], N, d, dv, B, W, knob, al("Q", "K", "V"), al("O"), al("dO"), out)
+        assert r["kind"] == want and out[0] == (W == 1), (dtype, N, W, knob, r["kind"], want)
+        ran.append(want)
+    assert ran == [MFMA, SIMT, SIMT, SIMT, F64, SIMT, F64]
+
+
 def test_unaligned_kv_views_fall_back(fa):
     """K / V views at an odd element offset (N % 8 == 0): not the 16-B path, same result."""
     def shifted(t):
