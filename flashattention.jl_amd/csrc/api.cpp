@@ -370,6 +370,37 @@ int fa_debug_local_bwd_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t
     return pl.kernel;
 }
 
+// The plans of a varlen call, in the shape of the local hooks: the plans treat kMaskVarlen
+// exactly as kMaskLocal (the class's default geometry, never a variant, never split, never p4,
+// never the single pass), and no plan depends on the lengths or the window.  forward out[8]:
+// varlen, causal bits, pad, ldk, nsplit, rows, grid, total; backward out[6] as the local hook.
+int fa_debug_varlen_fwd_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch,
+                             int kv_aligned16, int qo_aligned16, size_t ws_bytes, int cus, int64_t* out) {
+    if (!plan_args_ok(dtype, N, Nk, d, dv, batch, fa::kMaskLocal, false)) return -1;
+    const fa::DenseFwdPlan pl = fa::dense_fwd_plan(dtype, N, Nk, d, dv, batch, fa::kMaskVarlen, {fa::kFwdAuto, 0},
+                                                   kv_aligned16 != 0, qo_aligned16 != 0, ws_bytes, cus);
+    if (out) {
+        const int64_t f[8] = {pl.mask == fa::kMaskVarlen, pl.causal, pl.pad, pl.ldk, pl.nsplit, pl.rows, pl.grid, (int64_t)pl.total};
+        for (int i = 0; i < 8; ++i) out[i] = f[i];
+    }
+    return pl.kernel;
+}
+int fa_debug_varlen_bwd_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch,
+                             int qkvdo_aligned16, size_t ws_bytes, int cus, int64_t* out) {
+    if (!plan_args_ok(dtype, N, Nk, d, dv, batch, fa::kMaskLocal, true)) return -1;
+    const fa::DenseBwdPlan pl = fa::dense_bwd_plan(dtype, N, Nk, d, dv, batch, fa::kMaskVarlen,
+                                                   {0, fa::kBwdAuto, 3, -1}, qkvdo_aligned16 != 0, ws_bytes, cus);
+    if (out) {
+        const int64_t f[6] = {pl.padded, pl.N, pl.Nk, pl.d, pl.dv, (int64_t)pl.total};
+        for (int i = 0; i < 6; ++i) out[i] = f[i];
+    }
+    return pl.kernel;
+}
+static_assert(std::is_same<int32_t, int>::value, "include/fa_hip.h declares the varlen lengths as const int*");
+// Not part of the public header (tests): the clamp the varlen kernels apply to a caller's
+// length, fa::varlen_clamp(len, n) = min(max(len, 0), n).
+int fa_debug_varlen_clamp(int len, int n) { return fa::varlen_clamp(len, n); }
+
 // Not part of the public header: workgroups of the persistent strip backward (0 = one per
 // CU, the default; 1..4096 caps the grid).  Benchmark knob; returns the previous value.
 int fa_debug_set_win_bwd_grid(int v) {
@@ -424,14 +455,15 @@ static size_t dense_family_workspace(fa::DenseMask mask, bool bwd, int dtype, in
                : fa::dense_fwd_workspace(dtype, N, Nk, d, dv, batch, mask);
 }
 
-// fn: the public function's name.  The window (left, right) is read under kMaskLocal only; it
+// fn: the public function's name.  The window (left, right) is read under kMaskLocal and kMaskVarlen; it
 // stays int64_t down to the launchers (fa::mask_ints clamps it to [0, Nk] before it becomes a
 // 32-bit int) and changes neither a check nor a workspace answer.  takes_ws: false for
 // fa_dense_fwd, which has no workspace argument and runs what needs none.
 static int dense_family_fwd(fa::DenseMask mask, const char* fn, int dtype, const void* Q, const void* K,
                             const void* V, void* O, float* l, float* m, int64_t N, int64_t Nk, int64_t d,
                             int64_t dv, int64_t batch, int64_t left, int64_t right, float scale, bool takes_ws,
-                            void* workspace, size_t workspace_bytes, void* hip_stream) {
+                            void* workspace, size_t workspace_bytes, void* hip_stream,
+                            const int32_t* q_lens = nullptr, const int32_t* k_lens = nullptr) {
     if (!valid_dtype(dtype)) return fail(FA_ERR_INVALID_ARG, fn, "unknown dtype");
     if (N < 0 || Nk < 0 || d < 1 || dv < 1 || batch < 0)
         return fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: N, Nk, batch must be >= 0 and d, dv >= 1");
@@ -458,6 +490,8 @@ static int dense_family_fwd(fa::DenseMask mask, const char* fn, int dtype, const
     a.mask = mask;
     a.left = left;
     a.right = right;
+    a.q_lens = q_lens;   // device data, kMaskVarlen only: never read here
+    a.k_lens = k_lens;
     rc = fa::launch_dense_fwd(a, (hipStream_t)hip_stream, &why);
     return rc == FA_OK ? ok() : fail(rc, fn, why);
 }
@@ -466,7 +500,7 @@ static int dense_family_bwd(fa::DenseMask mask, const char* fn, int dtype, const
                             const void* V, const void* O, const void* dO, const float* l, const float* m, void* dQ,
                             void* dK, void* dV, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch,
                             int64_t left, int64_t right, float scale, void* workspace, size_t workspace_bytes,
-                            void* hip_stream) {
+                            void* hip_stream, const int32_t* q_lens = nullptr, const int32_t* k_lens = nullptr) {
     if (!valid_dtype(dtype)) return fail(FA_ERR_INVALID_ARG, fn, "unknown dtype");
     if (N < 0 || Nk < 0 || d < 1 || dv < 1 || batch < 0)
         return fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: N, Nk, batch must be >= 0 and d, dv >= 1");
@@ -500,6 +534,8 @@ static int dense_family_bwd(fa::DenseMask mask, const char* fn, int dtype, const
     a.mask = mask;
     a.left = left;
     a.right = right;
+    a.q_lens = q_lens;
+    a.k_lens = k_lens;
     rc = fa::launch_dense_bwd(a, (hipStream_t)hip_stream, &why);
     return rc == FA_OK ? ok() : fail(rc, fn, why);
 }
@@ -521,6 +557,12 @@ size_t fa_local_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64
 }
 size_t fa_local_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
     return dense_family_workspace(fa::kMaskLocal, true, dtype, N, Nk, d, dv, batch);
+}
+size_t fa_varlen_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
+    return dense_family_workspace(fa::kMaskVarlen, false, dtype, N, Nk, d, dv, batch);
+}
+size_t fa_varlen_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
+    return dense_family_workspace(fa::kMaskVarlen, true, dtype, N, Nk, d, dv, batch);
 }
 
 int fa_dense_fwd_ws(int dtype, const void* Q, const void* K, const void* V, void* O, float* l, float* m,
@@ -548,6 +590,14 @@ int fa_local_fwd(int dtype, const void* Q, const void* K, const void* V, void* O
                             scale, true, workspace, workspace_bytes, hip_stream);
 }
 
+int fa_varlen_fwd(int dtype, const void* Q, const void* K, const void* V, void* O, float* l, float* m,
+                  int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, const int32_t* q_lens,
+                  const int32_t* k_lens, int64_t left, int64_t right, float scale, void* workspace,
+                  size_t workspace_bytes, void* hip_stream) {
+    return dense_family_fwd(fa::kMaskVarlen, "fa_varlen_fwd", dtype, Q, K, V, O, l, m, N, Nk, d, dv, batch, left, right,
+                            scale, true, workspace, workspace_bytes, hip_stream, q_lens, k_lens);
+}
+
 int fa_dense_bwd(int dtype, const void* Q, const void* K, const void* V, const void* O, const void* dO,
                  const float* l, const float* m, void* dQ, void* dK, void* dV, int64_t N, int64_t Nk,
                  int64_t d, int64_t dv, int64_t batch, float scale, void* workspace,
@@ -568,6 +618,15 @@ int fa_local_bwd(int dtype, const void* Q, const void* K, const void* V, const v
                  void* workspace, size_t workspace_bytes, void* hip_stream) {
     return dense_family_bwd(fa::kMaskLocal, "fa_local_bwd", dtype, Q, K, V, O, dO, l, m, dQ, dK, dV, N, Nk, d, dv, batch,
                             left, right, scale, workspace, workspace_bytes, hip_stream);
+}
+
+int fa_varlen_bwd(int dtype, const void* Q, const void* K, const void* V, const void* O, const void* dO,
+                  const float* l, const float* m, void* dQ, void* dK, void* dV, int64_t N, int64_t Nk,
+                  int64_t d, int64_t dv, int64_t batch, const int32_t* q_lens, const int32_t* k_lens,
+                  int64_t left, int64_t right, float scale, void* workspace, size_t workspace_bytes,
+                  void* hip_stream) {
+    return dense_family_bwd(fa::kMaskVarlen, "fa_varlen_bwd", dtype, Q, K, V, O, dO, l, m, dQ, dK, dV, N, Nk, d, dv, batch,
+                            left, right, scale, workspace, workspace_bytes, hip_stream, q_lens, k_lens);
 }
 
 // Not part of the public header: launch order of the causal fast forward's query blocks

@@ -77,7 +77,28 @@ struct BwdParams {
     // sees keys i + off - left <= j <= i + off + right, both sides clamped to [0, Nk] of the
     // caller's extents, where Nk binds nowhere (mask_ints)
     int local = 0, left = 0, right = 0;
+    // varlen (fa_varlen_bwd; read by the kMaskVarlen instantiations only, which are LOCAL bodies):
+    // `batch` int32 lengths on the device (null = full), clamped to the caller's extents nqv / nkv
+    // (the padded path rounds N and Nk up); off is then per slab, nk - nq (bwd_ext)
+    const int32_t *q_lens = nullptr, *k_lens = nullptr;
+    int nqv = 0;
 };
+
+// The extents of slab b in the bounds of a masked kernel: the launch's own (N, Nk as run, off
+// and the window from the host), or under VARLEN the slab's (varlen_extents).  Strides stay
+// p.N / p.Nk.  Rows >= nq carry nlse = -inf from the varlen pre-pass (P = 0 exactly), so the
+// kernels only trim their loops at nq; keys >= nk are selected to -inf where S is formed.
+template <bool VARLEN>
+__device__ __forceinline__ VarlenExt bwd_ext(const BwdParams& p, int b) {
+    if constexpr (VARLEN) return varlen_extents(p.q_lens, p.k_lens, b, p.nqv, p.nkv, p.left, p.right);
+    return VarlenExt{p.N, p.Nk, p.off, p.left, p.right};
+}
+// `rows` zero rows of a [C][ld] slab from row r0 (clipped at ld), by the whole workgroup
+template <class T>
+__device__ __forceinline__ void zero_rows(T* slab, int ld, int C, int r0, int rows, int nthreads) {
+    const int n = min(rows, ld - r0);
+    for (int i = threadIdx.x; i < n * C; i += nthreads) slab[(int64_t)(i / n) * ld + r0 + i % n] = (T)0.0f;
+}
 
 constexpr unsigned kBwdHdrMagic = 0x46414200u;   // "FAB\0"
 
@@ -121,6 +142,33 @@ __global__ __launch_bounds__(256) void bwd_prepass_v(BwdParams p) {
     prepass_rows8((const T*)p.O, (const T*)p.dO, p.l, p.m, p.nD, p.nlse, g8 * 8, p.N, p.dv, p.scale);
 }
 
+// Varlen pre-pass (every 16/32-bit fa_varlen_bwd; one thread per (b, n) as bwd_prepass).  A row
+// n >= nq, or a query that sees no key (its window [n + off - left, n + off + right] misses
+// [0, nk)), gets nD = 0 and nlse = -inf, chosen from the lengths and the window, never from the
+// caller's l: (s + nlse) c is then -inf for any finite score and P = exp2(-inf) = 0 exactly,
+// where -(m + ln l)/tau of the empty-row state (-inf, 0) would be +inf.
+template <class T>
+__global__ __launch_bounds__(256) void bwd_prepass_varlen(BwdParams p) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t total = (int64_t)p.N * p.batch;
+    if (idx >= total) return;
+    if (idx == 0) write_bwd_header(p);
+    const int64_t b = idx / p.N, n = idx - b * p.N;
+    const VarlenExt e = varlen_extents(p.q_lens, p.k_lens, (int)b, p.nqv, p.nkv, p.left, p.right);
+    const int i = (int)n;
+    if (i >= e.nq || max(0, i + e.off - e.left) > min(e.nk - 1, i + e.off + e.right)) {
+        p.nD[idx] = 0.0f;
+        p.nlse[idx] = kNegInf;
+        return;
+    }
+    const T* O = (const T*)p.O + b * (int64_t)p.N * p.dv + n;
+    const T* dO = (const T*)p.dO + b * (int64_t)p.N * p.dv + n;
+    float acc = 0.0f;
+    for (int c = 0; c < p.dv; ++c) acc = fmaf((float)dO[(int64_t)c * p.N], (float)O[(int64_t)c * p.N], acc);
+    p.nD[idx] = -acc;
+    p.nlse[idx] = -(p.m[idx] + logf(p.l[idx])) / p.scale;
+}
+
 // --------------------------------------------------------------------------
 // 2./3. generic SIMT path.  Tiles of 32 queries x 32 keys in LDS, arithmetic in
 // A: float for the 16/32-bit types, double for Float64 (whose row statistics
@@ -133,7 +181,7 @@ constexpr int kGThreads = 256;
 // dQ: one block per (b, 32-query tile).
 template <class T, class A, DenseMask MASK = kMaskNone>
 __global__ __launch_bounds__(kGThreads) void bwd_generic_dq(BwdParams p) {
-    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal;
+    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal || MASK == kMaskVarlen, VARLEN = MASK == kMaskVarlen;
     extern __shared__ __attribute__((aligned(16))) char gsm_raw[];
     A* const gsm = (A*)gsm_raw;
     const int d = p.d, dv = p.dv, N = p.N, Nk = p.Nk, ld = d + 1, ldv = dv + 1;
@@ -165,12 +213,13 @@ __global__ __launch_bounds__(kGThreads) void bwd_generic_dq(BwdParams p) {
     const A* nD = (const A*)p.nD + (int64_t)b * N;
     const A* nL = (const A*)p.nlse + (int64_t)b * N;
     const A sl2 = scale_log2_a<A>(p.scale_log2, p.scale64);
+    const VarlenExt x = bwd_ext<VARLEN>(p, b);   // VARLEN: the slab's extents (else N, Nk, p.off, the window)
     int kend = Nk;   // causal: keys up to the tile's last real query's limit
     if constexpr (CAUSAL) kend = min(Nk, min(q0 + kGT - 1, N - 1) + p.off + 1);
     int kbeg = 0;    // local: from the tile's first query's left edge to its last real query's right edge
-    if constexpr (LOCAL) {
-        kbeg = max(0, q0 + p.off - p.left) / kGT * kGT;
-        kend = min(Nk, min(q0 + kGT - 1, N - 1) + p.off + p.right + 1);
+    if constexpr (LOCAL) {   // (VARLEN: no step for a tile past nq or whose queries see no key; zeros are stored)
+        kbeg = max(0, q0 + x.off - x.left) / kGT * kGT;
+        kend = min(x.nk, min(q0 + kGT - 1, x.nq - 1) + x.off + x.right + 1);
     }
     for (int k0 = kbeg; k0 < kend; k0 += kGT) {
         __syncthreads();
@@ -188,7 +237,8 @@ __global__ __launch_bounds__(kGThreads) void bwd_generic_dq(BwdParams p) {
             A ds = (A)0;
             bool vis = q0 + q < N && k0 + k < Nk;
             if constexpr (CAUSAL) vis = vis && k0 + k <= q0 + q + p.off;
-            if constexpr (LOCAL) vis = vis && k0 + k <= q0 + q + p.off + p.right && k0 + k >= q0 + q + p.off - p.left;
+            if constexpr (LOCAL) vis = vis && k0 + k <= q0 + q + x.off + x.right && k0 + k >= q0 + q + x.off - x.left;
+            if constexpr (VARLEN) vis = vis && q0 + q < x.nq && k0 + k < x.nk;
             if (vis) {
                 A s = (A)0, dp = (A)0;
                 for (int f = 0; f < d; ++f) s = fma_a(sQ[q * ld + f], sK[k * ld + f], s);
@@ -221,7 +271,7 @@ __global__ __launch_bounds__(kGThreads) void bwd_generic_dq(BwdParams p) {
 // dK, dV: one block per (b, 32-key tile).
 template <class T, class A, DenseMask MASK = kMaskNone>
 __global__ __launch_bounds__(kGThreads) void bwd_generic_dkdv(BwdParams p) {
-    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal;
+    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal || MASK == kMaskVarlen, VARLEN = MASK == kMaskVarlen;
     extern __shared__ __attribute__((aligned(16))) char gsm_raw[];
     A* const gsm = (A*)gsm_raw;
     const int d = p.d, dv = p.dv, N = p.N, Nk = p.Nk, ld = d + 1, ldv = dv + 1;
@@ -258,9 +308,11 @@ __global__ __launch_bounds__(kGThreads) void bwd_generic_dkdv(BwdParams p) {
     // local: the queries i that see some key of the tile, k0 - off - right <= i <= k0 + 31 - off + left;
     // none for keys left of every window (the loop then runs no step and zeros are stored)
     int qend = N;
+    const VarlenExt x = bwd_ext<VARLEN>(p, b);
     if constexpr (LOCAL) {
-        qbeg = max(0, k0 - p.off - p.right) / kGT * kGT;
-        qend = min(N, k0 + kGT - 1 - p.off + p.left + 1);
+        qbeg = max(0, k0 - x.off - x.right) / kGT * kGT;
+        qend = min(x.nq, k0 + kGT - 1 - x.off + x.left + 1);
+        if (VARLEN && k0 >= x.nk) qend = 0;   // a tile past nk: zeros are stored
     }
     for (int q0 = qbeg; q0 < qend; q0 += kGT) {
         __syncthreads();
@@ -278,7 +330,8 @@ __global__ __launch_bounds__(kGThreads) void bwd_generic_dkdv(BwdParams p) {
             A pr = (A)0, ds = (A)0;
             bool vis = q0 + q < N && k0 + k < Nk;
             if constexpr (CAUSAL) vis = vis && k0 + k <= q0 + q + p.off;
-            if constexpr (LOCAL) vis = vis && k0 + k <= q0 + q + p.off + p.right && k0 + k >= q0 + q + p.off - p.left;
+            if constexpr (LOCAL) vis = vis && k0 + k <= q0 + q + x.off + x.right && k0 + k >= q0 + q + x.off - x.left;
+            if constexpr (VARLEN) vis = vis && q0 + q < x.nq && k0 + k < x.nk;
             if (vis) {
                 A s = (A)0, dp = (A)0;
                 for (int f = 0; f < d; ++f) s = fma_a(sQ[q * ld + f], sK[k * ld + f], s);
@@ -339,7 +392,7 @@ constexpr int kF32R = 33;   // LDS row (floats)
 
 template <int D, int DV, DenseMask MASK = kMaskNone>
 __global__ __launch_bounds__(256) void bwd_dkdv_f32(BwdParams p) {
-    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal;
+    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal || MASK == kMaskVarlen, VARLEN = MASK == kMaskVarlen;
     __shared__ float sQ[D * kF32R], sdO[DV * kF32R], sL[kF32T], sD[kF32T];
     const int N = p.N, Nk = p.Nk, d = p.d, dv = p.dv;
     const int nkb = (Nk + 127) / 128;
@@ -370,9 +423,11 @@ __global__ __launch_bounds__(256) void bwd_dkdv_f32(BwdParams p) {
     int qbeg = 0;   // causal: the first query tile that sees the block's first key
     if constexpr (CAUSAL) qbeg = max(0, k0 - p.off) / kF32T * kF32T;
     int qend = N;   // local: the queries that see some key of the block (none: zeros are stored)
+    const VarlenExt e = bwd_ext<VARLEN>(p, b);
     if constexpr (LOCAL) {
-        qbeg = max(0, k0 - p.off - p.right) / kF32T * kF32T;
-        qend = min(N, k0 + 127 - p.off + p.left + 1);
+        qbeg = max(0, k0 - e.off - e.right) / kF32T * kF32T;
+        qend = min(e.nq, k0 + 127 - e.off + e.left + 1);
+        if (VARLEN && k0 >= e.nk) qend = 0;   // a block past nk: zeros are stored
     }
     for (int q0 = qbeg; q0 < qend; q0 += kF32T) {
         __syncthreads();
@@ -404,7 +459,10 @@ __global__ __launch_bounds__(256) void bwd_dkdv_f32(BwdParams p) {
                 if (key > q0 + q + p.off) sa[x] = kNegInf;
             }
             if constexpr (LOCAL) {
-                if (key > q0 + q + p.off + p.right || key < q0 + q + p.off - p.left) sa[x] = kNegInf;
+                if (key > q0 + q + e.off + e.right || key < q0 + q + e.off - e.left) sa[x] = kNegInf;
+            }
+            if constexpr (VARLEN) {   // the key column past nk (rows past nq carry sL = -inf)
+                if (key >= e.nk) sa[x] = kNegInf;
             }
             const float pr = exp2f((sa[x] + sL[q]) * c);
             sa[x] = pr;                          // P
@@ -441,7 +499,7 @@ __global__ __launch_bounds__(256) void bwd_dkdv_f32(BwdParams p) {
 
 template <int D, int DV, DenseMask MASK = kMaskNone>
 __global__ __launch_bounds__(256) void bwd_dq_f32(BwdParams p) {
-    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal;
+    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal || MASK == kMaskVarlen, VARLEN = MASK == kMaskVarlen;
     __shared__ float sK[D * kF32R], sV[DV * kF32R];
     const int N = p.N, Nk = p.Nk, d = p.d, dv = p.dv;
     const int nqb = (N + 127) / 128;
@@ -468,9 +526,10 @@ __global__ __launch_bounds__(256) void bwd_dq_f32(BwdParams p) {
     int kend = Nk;   // causal: keys up to the block's last real query's limit
     if constexpr (CAUSAL) kend = min(Nk, min(q0 + 127, N - 1) + p.off + 1);
     int kbeg = 0;   // local: from the block's first query's left edge to its last real query's right edge
-    if constexpr (LOCAL) {
-        kbeg = max(0, q0 + p.off - p.left) / kF32T * kF32T;
-        kend = min(Nk, min(q0 + 127, N - 1) + p.off + p.right + 1);
+    const VarlenExt e = bwd_ext<VARLEN>(p, b);
+    if constexpr (LOCAL) {   // (VARLEN: possibly no step; zeros are stored)
+        kbeg = max(0, q0 + e.off - e.left) / kF32T * kF32T;
+        kend = min(e.nk, min(q0 + 127, e.nq - 1) + e.off + e.right + 1);
     }
     for (int k0 = kbeg; k0 < kend; k0 += kF32T) {
         __syncthreads();
@@ -497,9 +556,9 @@ __global__ __launch_bounds__(256) void bwd_dq_f32(BwdParams p) {
                 if (k0 + acc_row(x, h) > qi + p.off) sa[x] = kNegInf;
             }
             if constexpr (LOCAL) {
-                if (k0 + acc_row(x, h) > qi + p.off + p.right || k0 + acc_row(x, h) < qi + p.off - p.left) sa[x] = kNegInf;
+                if (k0 + acc_row(x, h) > qi + e.off + e.right || k0 + acc_row(x, h) < qi + e.off - e.left) sa[x] = kNegInf;
             }
-            if (k0 + kF32T > Nk && k0 + acc_row(x, h) >= Nk) sa[x] = kNegInf;   // the ragged last tile
+            if (k0 + kF32T > e.nk && k0 + acc_row(x, h) >= e.nk) sa[x] = kNegInf;   // the ragged last tile
             const float pr = exp2f((sa[x] + nlq) * c);
             pa[x] = pr * (pa[x] + ndq);          // dSᵀ
         }
@@ -624,7 +683,7 @@ __device__ void fused_combine(const BwdParams& p, int b, int qb) {
 // its own band, and S is selected to -inf on the tiles that straddle either of its diagonals.
 template <class T, int D, int DV, DenseMask MASK = kMaskNone>
 __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
-    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal;
+    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal || MASK == kMaskVarlen, VARLEN = MASK == kMaskVarlen;
     typedef typename Frag8<T>::type F8;
     constexpr int KB = D * 128, VB = DV * 128, STAGE = KB + VB;
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
@@ -641,6 +700,20 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
     }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     const int N = p.N, Nk = p.Nk;
+    // key tiles [tbeg, NT) of the block, from the slab's extents (bwd_ext).  VARLEN: a block past
+    // nq, or whose queries see no key, stores zeros and leaves before any load or barrier
+    const VarlenExt e = bwd_ext<VARLEN>(p, b);
+    int vtbeg = 0, vNT = 0;   // VARLEN: the tile range, here; the other masks compute theirs below, as before
+    if constexpr (VARLEN) {
+        const int hi = min(qb * 128 + 127, e.nq - 1) + e.off + e.right;
+        vtbeg = max(0, qb * 128 + e.off - e.left) / 64;
+        vNT = hi < 0 ? 0 : min((e.nk + 63) / 64, hi / 64 + 1);
+        if (qb * 128 >= e.nq || vtbeg >= vNT) {
+            zero_rows((T*)p.dQ + (int64_t)b * N * D, N, D, qb * 128, 128, 256);
+            return;
+        }
+    }
+    auto NKV = [&] { if constexpr (VARLEN) return e.nk; else return p.nkv; };
     const auto qrs = bslab<T>(p.Q, (int64_t)b * N * D, (int64_t)N * D);
     const auto ors = bslab<T>(p.dO, (int64_t)b * N * DV, (int64_t)N * DV);
     const auto krs = bslab<T>(p.K, (int64_t)b * Nk * D, (int64_t)Nk * D);
@@ -675,17 +748,17 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
         dma_image<DV>(vrs, st + KB, Nk, t * 64, wave, lane);
     };
     int wlim0 = 0;   // causal: the key limit (query row + off) of the wave's first query, a scalar
-    if constexpr (CAUSAL || LOCAL) wlim0 = qb * 128 + __builtin_amdgcn_readfirstlane(wave) * 32 + p.off;
+    if constexpr (CAUSAL || LOCAL) wlim0 = qb * 128 + __builtin_amdgcn_readfirstlane(wave) * 32 + e.off;
     auto compute = [&](const char* st, int t) {
         if constexpr (CAUSAL) {
             if (t * 64 > wlim0 + 31) return;   // wave-uniform: no query of the wave sees the tile
         }
         if constexpr (LOCAL) {   // ... on either side
-            if (t * 64 > wlim0 + 31 + p.right || t * 64 + 63 < wlim0 - p.left) return;
+            if (t * 64 > wlim0 + 31 + e.right || t * 64 + 63 < wlim0 - e.left) return;
         }
         const char* kimg = st;
         const char* vimg = st + KB;
-        const bool partial = (t + 1) * 64 > p.nkv;
+        const bool partial = (t + 1) * 64 > NKV();
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
             f32x16 sa, dp;
@@ -698,7 +771,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
             if (partial) {
 #pragma unroll
                 for (int x = 0; x < 16; ++x)
-                    if (t * 64 + kb * 32 + (x & 7) + 8 * h + 16 * (x >> 3) >= p.nkv) sa[x] = kNegInf;
+                    if (t * 64 + kb * 32 + (x & 7) + 8 * h + 16 * (x >> 3) >= NKV()) sa[x] = kNegInf;
             }
             if constexpr (CAUSAL) {
                 const int w0 = wlim0 - t * 64 - kb * 32;   // ... relative to the 32-key block
@@ -711,7 +784,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
             }
             if constexpr (LOCAL) {
                 // wr, wl: the right and left key limits of the wave's first query, relative to the 32-key block
-                const int wr = wlim0 + p.right - t * 64 - kb * 32, wl = wlim0 - p.left - t * 64 - kb * 32;
+                const int wr = wlim0 + e.right - t * 64 - kb * 32, wl = wlim0 - e.left - t * 64 - kb * 32;
                 if (31 > wr) {           // a key past the first query's right limit
                     const int lr = r - 8 * h + wr;
 #pragma unroll
@@ -741,10 +814,11 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
     int NT = (Nk + 63) / 64;
     if constexpr (CAUSAL) NT = min(NT, (min(qb * 128 + 127, N - 1) + p.off) / 64 + 1);
     int tbeg = 0;   // local: key tiles [tbeg, NT), never empty (the key i + off of the first query lies in both)
-    if constexpr (LOCAL) {
+    if constexpr (LOCAL && !VARLEN) {
         tbeg = max(0, qb * 128 + p.off - p.left) / 64;
         NT = min(NT, (min(qb * 128 + 127, N - 1) + p.off + p.right) / 64 + 1);
     }
+    if constexpr (VARLEN) { tbeg = vtbeg; NT = vNT; }
     char* const st0 = smem;
     char* const st1 = smem + STAGE;
     fill(st0, tbeg);
@@ -782,7 +856,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_fast(BwdParams p) {
 // selects on the tiles that straddle either diagonal.
 template <class T, int D, int DV, DenseMask MASK = kMaskNone>
 __global__ __launch_bounds__(256, 2) void bwd_dkdv_fast(BwdParams p) {
-    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal;
+    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal || MASK == kMaskVarlen, VARLEN = MASK == kMaskVarlen;
     typedef typename Frag8<T>::type F8;
     constexpr int QB = D * 128, OB = DV * 128, STAGE = QB + OB + 512;
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
@@ -794,6 +868,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_fast(BwdParams p) {
     const auto ors = bslab<T>(p.dO, (int64_t)b * N * DV, (int64_t)N * DV);
     const auto krs = bslab<T>(p.K, (int64_t)b * Nk * D, (int64_t)Nk * D);
     const auto vrs = bslab<T>(p.V, (int64_t)b * Nk * DV, (int64_t)Nk * DV);
+    const VarlenExt e = bwd_ext<VARLEN>(p, b);
     const int kj = kblk * 128 + wave * 32 + r;   // this lane's key (column of S, dP)
     F8 kf[D / 16], vf[DV / 16];
 #pragma unroll
@@ -837,13 +912,13 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_fast(BwdParams p) {
         dma_image<DV>(ors, st + QB, N, t * 64, wave, lane);
     };
     int wk0 = 0;   // causal: the wave's first key minus off (the first query that sees it), a scalar
-    if constexpr (CAUSAL || LOCAL) wk0 = kblk * 128 + __builtin_amdgcn_readfirstlane(wave) * 32 - p.off;
+    if constexpr (CAUSAL || LOCAL) wk0 = kblk * 128 + __builtin_amdgcn_readfirstlane(wave) * 32 - e.off;
     auto compute = [&](const char* st, int t) {
         if constexpr (CAUSAL) {
             if (t * 64 + 63 < wk0) return;   // wave-uniform: no query of the tile sees the wave's keys
         }
         if constexpr (LOCAL) {
-            if (t * 64 + 63 < wk0 - p.right || t * 64 > wk0 + 31 + p.left) return;
+            if (t * 64 + 63 < wk0 - e.right || t * 64 > wk0 + 31 + e.left) return;
         }
         const char* qimg = st;
         const char* oimg = st + QB;
@@ -881,19 +956,32 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_fast(BwdParams p) {
                 // query row q0 + ql (relative to the wave's first key minus off) sees key r iff
                 // q0 + ql - left <= r <= q0 + ql + right; lane terms rebuilt from the lane id as above
                 const int q0 = t * 64 + u * 32 - wk0;
-                if (q0 + p.right < 31) {            // the block's first row misses the wave's last key on the right
+                if (q0 + e.right < 31) {            // the block's first row misses the wave's last key on the right
                     const int ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-                    const int lk = (ln & 31) - 8 * (ln >> 5) - q0 - p.right;
+                    const int lk = (ln & 31) - 8 * (ln >> 5) - q0 - e.right;
 #pragma unroll
                     for (int x = 0; x < 16; ++x)
                         if ((x & 7) + 16 * (x >> 3) < lk) sa[x] = kNegInf;
                 }
-                if (q0 + 31 > p.left) {             // its last row misses the wave's first key on the left
+                if (q0 + 31 > e.left) {             // its last row misses the wave's first key on the left
                     const int ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-                    const int lk = (ln & 31) - 8 * (ln >> 5) - q0 + p.left;
+                    const int lk = (ln & 31) - 8 * (ln >> 5) - q0 + e.left;
 #pragma unroll
                     for (int x = 0; x < 16; ++x)
                         if ((x & 7) + 16 * (x >> 3) > lk) sa[x] = kNegInf;
+                }
+            }
+            if constexpr (VARLEN) {
+                // the key column at nk: these rows are the caller's and are written, so a key
+                // >= nk gets P = 0 in every row (only in the wave that holds nk: wave-uniform test;
+                // rows >= nq carry -lse = -inf from the pre-pass)
+                const int wkey = kblk * 128 + __builtin_amdgcn_readfirstlane(wave) * 32;
+                if (wkey + 31 >= e.nk) {
+                    const int ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+                    if (wkey + (ln & 31) >= e.nk) {
+#pragma unroll
+                        for (int x = 0; x < 16; ++x) sa[x] = kNegInf;
+                    }
                 }
             }
             F8 pf[2], dsf[2];
@@ -914,16 +1002,17 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_fast(BwdParams p) {
         }
     };
 
-    const int NT = (N + 63) / 64;
+    const int NT = ((VARLEN ? e.nq : N) + 63) / 64;
     char* const st0 = smem;
     char* const st1 = smem + STAGE;
     int t0 = 0;   // causal: the first query tile that sees the block's first key (< NT: see DESIGN §2.7)
     if constexpr (CAUSAL) t0 = min(max(0, kblk * 128 - p.off) / 64, NT - 1);
     int t1 = NT;   // local: query tiles [t0, t1), possibly none
     if constexpr (LOCAL) {
-        const int qhi = kblk * 128 + 127 - p.off + p.left;   // the last query that sees the block's last key
-        t0 = max(0, kblk * 128 - p.off - p.right) / 64;
+        const int qhi = kblk * 128 + 127 - e.off + e.left;   // the last query that sees the block's last key
+        t0 = max(0, kblk * 128 - e.off - e.right) / 64;
         t1 = qhi < 0 ? 0 : min(NT, qhi / 64 + 1);
+        if (VARLEN && kblk * 128 >= e.nk) t1 = 0;   // a block past nk: no tile, zeros are stored
     }
     if (!LOCAL || t0 < t1) {   // (block-uniform: no prefetch of a tile that does not exist, no uneven barrier)
         load_rowc(t0);
@@ -1816,6 +1905,17 @@ static hipError_t launch_generic(const BwdParams& p, DenseMask mask, hipStream_t
 template <class T>
 static hipError_t launch_typed(const DenseBwdPlan& pl, const BwdParams& p, DenseMask mask, hipStream_t s) {
     const int64_t total = (int64_t)p.N * p.batch;
+    if (mask == kMaskVarlen) {   // its own pre-pass: the empty rows come from the lengths (bwd_prepass_varlen)
+        hipLaunchKernelGGL(bwd_prepass_varlen<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p);
+        const hipError_t ev = hipGetLastError();
+        if (ev != hipSuccess) return ev;
+        if constexpr (std::is_same<T, float>::value) {
+            if (pl.kernel == kDenseBwdF32Mfma) return launch_f32_mfma(p, mask, s);
+        } else {
+            if (pl.kernel == kDenseBwdTwoPass) return launch_fast<T>(pl, p, mask, s);
+        }
+        return launch_generic<T>(p, mask, s);
+    }
     bool vec = false;
     if constexpr (sizeof(T) == 2) {
         vec = p.N % 8 == 0 && aligned16(p.O) && aligned16(p.dO);
@@ -1911,7 +2011,8 @@ int launch_dense_bwd(const DenseBwdArgs& a, hipStream_t s, const char** why) {
     // causal, local and Float64 totals depend on the shape alone: the whole of it must be there.
     // (A padded call checks its slabs below; the single pass's part is optional.)
     if ((a.mask != kMaskNone || a.dtype == FA_DTYPE_F64) && a.workspace_bytes < pl.total) {
-        *why = a.mask == kMaskLocal    ? "workspace smaller than fa_local_bwd_workspace()"
+        *why = a.mask == kMaskVarlen   ? "workspace smaller than fa_varlen_bwd_workspace()"
+               : a.mask == kMaskLocal  ? "workspace smaller than fa_local_bwd_workspace()"
                : a.mask == kMaskCausal ? "workspace smaller than fa_causal_bwd_workspace()"
                                        : "workspace smaller than fa_dense_bwd_workspace()";
         return FA_ERR_WORKSPACE;
@@ -1927,6 +2028,8 @@ int launch_dense_bwd(const DenseBwdArgs& a, hipStream_t s, const char** why) {
     p.nlse = (float*)(w + pl.off_nlse);
     p.N = (int)a.N; p.Nk = (int)a.Nk; p.d = (int)a.d; p.dv = (int)a.dv; p.batch = (int)a.batch;
     p.nkv = (int)a.Nk;   // stays the caller's on the padded path
+    p.nqv = (int)a.N;    // likewise
+    p.q_lens = a.q_lens; p.k_lens = a.k_lens;
     p.scale = a.scale;
     p.scale_log2 = a.scale * kLog2e;
     hipError_t e;

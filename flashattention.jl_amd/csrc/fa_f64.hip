@@ -40,6 +40,9 @@ struct F64Params {
     int causal = 0, off = 0;   // CAUSAL instantiations: query i sees keys j <= i + off (off = Nk - N)
     // LOCAL instantiations: keys i + off - left <= j <= i + off + right, each side in [0, Nk] (mask_ints)
     int local = 0, left = 0, right = 0;
+    // kMaskVarlen instantiations (LOCAL bodies): `batch` int32 lengths on the device (null = full);
+    // off is then per slab, nk - nq (varlen_extents)
+    const int32_t *q_lens = nullptr, *k_lens = nullptr;
 };
 
 constexpr int kQB64 = 64;    // queries per workgroup (QB = 16 for grids smaller than the chip)
@@ -57,7 +60,7 @@ static size_t f64_lds_bytes(int d, int dv, bool stats, int QB) {
 // keys KPG·g .. KPG·g + KPG−1 of each tile and owns output channels g, g + NG, ….
 template <bool STATS, int QB, DenseMask MASK = kMaskNone>
 __global__ __launch_bounds__(kTh64) void dense_fwd_f64(F64Params p) {
-    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal;
+    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal || MASK == kMaskVarlen, VARLEN = MASK == kMaskVarlen;
     constexpr int NG = kTh64 / QB, KPG = kKB64 / NG, OPER = kMaxHeadDim / NG;
     static_assert(KPG >= 1 && QB * NG == kTh64, "geometry");
     extern __shared__ __attribute__((aligned(16))) double sm64[];
@@ -89,10 +92,15 @@ __global__ __launch_bounds__(kTh64) void dense_fwd_f64(F64Params p) {
     // local: from the workgroup's first query's left edge to its last real query's right edge.  A
     // query whose window begins in a later tile has m_run = -inf after a tile: its alpha is 1
     // and its P are 0 there (not the NaN of -inf - -inf)
+    // varlen: the slab's own extents, off of either sign; a workgroup past nq or whose queries see
+    // no key runs no tile, and a row without a key (m_run = -inf, l_run = 0 at the end) or past nq
+    // leaves as the empty-row state O = 0, l = 0, m = -inf (STATS: nlse = -inf, P = 0 exactly)
     int kbeg = 0;
+    VarlenExt e{N, Nk, p.off, p.left, p.right};
+    if constexpr (VARLEN) e = varlen_extents(p.q_lens, p.k_lens, b, N, Nk, p.left, p.right);
     if constexpr (LOCAL) {
-        kbeg = max(0, q0 + p.off - p.left) / kKB64 * kKB64;
-        kend = min(Nk, min(q0 + QB - 1, N - 1) + p.off + p.right + 1);
+        kbeg = max(0, q0 + e.off - e.left) / kKB64 * kKB64;
+        kend = min(e.nk, min(q0 + QB - 1, e.nq - 1) + e.off + e.right + 1);
     }
     for (int k0 = kbeg; k0 < kend; k0 += kKB64) {
         __syncthreads();   // the previous tile's K / V / P readers are done
@@ -123,7 +131,8 @@ __global__ __launch_bounds__(kTh64) void dense_fwd_f64(F64Params p) {
             bool vis = k0 + KPG * g + j < Nk;
             if constexpr (CAUSAL) vis = vis && k0 + KPG * g + j <= q0 + qi + p.off;
             if constexpr (LOCAL)
-                vis = vis && k0 + KPG * g + j <= q0 + qi + p.off + p.right && k0 + KPG * g + j >= q0 + qi + p.off - p.left;
+                vis = vis && k0 + KPG * g + j <= q0 + qi + e.off + e.right && k0 + KPG * g + j >= q0 + qi + e.off - e.left;
+            if constexpr (VARLEN) vis = vis && k0 + KPG * g + j < e.nk;
             s[j] = vis ? s[j] * p.scale : -__builtin_huge_val();
             mx = dmax(mx, s[j]);
         }
@@ -171,11 +180,20 @@ __global__ __launch_bounds__(kTh64) void dense_fwd_f64(F64Params p) {
 
     const int n = q0 + qi;
     if (n >= N) return;
+    const bool live = !VARLEN || (n < e.nq && l_run > 0.0);
     if (STATS) {
-        if (g == 0) p.nlse[(int64_t)b * N + n] = -(m_run + log(l_run)) / p.scale;
+        if (g == 0) p.nlse[(int64_t)b * N + n] = live ? -(m_run + log(l_run)) / p.scale : -__builtin_huge_val();
         return;
     }
-    const double inv = 1.0 / l_run;
+    if constexpr (VARLEN) {
+        if (!live) {
+#pragma unroll
+            for (int i = 0; i < OPER; ++i) o[i] = 0.0;
+            m_run = -__builtin_huge_val();
+            l_run = 0.0;
+        }
+    }
+    const double inv = live ? 1.0 / l_run : 0.0;
     double* Ob = p.O + (int64_t)b * N * dv;
 #pragma unroll
     for (int i = 0; i < OPER; ++i) {
@@ -248,6 +266,7 @@ int launch_dense_fwd_f64(const DenseArgs& a, hipStream_t s, const char** why) {
     p.nqb = (int)((a.N + kQB64 - 1) / kQB64);
     p.scale = a.scale64 > 0.0 ? a.scale64 : (double)a.scale;
     set_mask(p, a.mask, a.left, a.right, a.N, a.Nk);
+    p.q_lens = a.q_lens; p.k_lens = a.k_lens;
     const hipError_t e = launch_f64_kernel<false>(p, a.batch, a.mask, s);
     if (e != hipSuccess) {
         *why = hipGetErrorString(e);
@@ -265,6 +284,7 @@ int launch_f64_bwd_stats(const DenseBwdArgs& a, double* nD, double* nlse, hipStr
     p.nqb = (int)((a.N + kQB64 - 1) / kQB64);
     p.scale = a.scale64 > 0.0 ? a.scale64 : (double)a.scale;
     set_mask(p, a.mask, a.left, a.right, a.N, a.Nk);
+    p.q_lens = a.q_lens; p.k_lens = a.k_lens;
     hipError_t e = launch_f64_kernel<true>(p, a.batch, a.mask, s);
     if (e == hipSuccess) {
         const int64_t total = a.N * a.batch;

@@ -140,12 +140,48 @@ __device__ __forceinline__ int local_ntiles(int nt, int q_last, int N, int off, 
     return min(nt, (min(q_last, N - 1) + off + wright) / bn + 1);
 }
 
+// Varlen launches (fa_varlen_fwd; kMaskVarlen instantiations, which are LOCAL bodies): slab b is
+// the leading nq = q_lens[b] queries and nk = k_lens[b] keys of its (N, Nk) slab, off = nk - nq
+// of either sign, the window clamped per slab (varlen_extents).  N and ldk stay the strides; nq,
+// nk and off replace N, Nk and Nk - N in every bound.  What fa_local_fwd rules out now happens:
+// a query i < nq sees no key when i + off + right < 0 (nk < nq under a right bound) or nk = 0,
+// rows i >= nq are not queries at all, and a workgroup's tile range can be empty.  The rows
+// without a key keep m = -inf, l = 0 and O = 0 through the LOCAL bodies (alpha = 1, exponent
+// offset 0, P = exp2(-inf) = 0), and the epilogues store exactly that state: O = 0, l = 0,
+// m = -inf, by a select on (row < nq and l > 0), never a division by l = 0.
+// The last tile + 1 of a workgroup with query rows .. q_last: 0 when its last query's right
+// limit is negative (local_ntiles divides a negative number towards zero).
+__device__ __forceinline__ int varlen_ntiles(int nt, int q_last, int nq, int off, int wright, int bn) {
+    const int hi = min(q_last, nq - 1) + off + wright;
+    return hi < 0 ? 0 : min(nt, hi / bn + 1);
+}
+// The empty-row state of the rows [q0, q0 + rows) below N of slab b: O = 0, l = 0, m = -inf.
+template <class T>
+__device__ __forceinline__ void store_empty_rows(const FwdParams& p, int b, int q0, int rows, int nthreads) {
+    const int N = p.N, dv = p.dv, n = min(rows, N - q0);
+    T* const Ob = (T*)p.O + (int64_t)b * N * dv;
+    for (int i = threadIdx.x; i < n * dv; i += nthreads) Ob[(int64_t)(i / n) * N + q0 + i % n] = (T)0.0f;
+    for (int i = threadIdx.x; i < n; i += nthreads) {
+        p.l[(int64_t)b * N + q0 + i] = 0.0f;
+        p.m[(int64_t)b * N + q0 + i] = kNegInf;
+    }
+}
+
+// N's and Nk's roles as BOUNDS in the masked bodies below (strides stay N, Nk / ldk): the launch's
+// own extents, Nk - N and window, or under VARLEN the slab's (`ve`, varlen_extents).  Macros, not
+// variables or lambdas: each expands to the parent's own expression at its use, so the dense,
+// causal and local instantiations compile to the code they had (tools/asm_same.py).
+#define FA_NKE (VARLEN ? ve.nk : Nk)
+#define FA_OFF (VARLEN ? ve.off : (Nk - N))
+#define FA_WL (VARLEN ? ve.left : p.wleft)
+#define FA_WR (VARLEN ? ve.right : p.wright)
+
 // --------------------------------------------------------------------------
 // bf16 / fp16 forward (v_mfma_f32_32x32x16_{bf16,f16})
 // --------------------------------------------------------------------------
 template <class T, int D, int DV, DenseMask MASK = kMaskNone>
 __global__ __launch_bounds__(kThreads) void dense_fwd_generic(FwdParams p) {
-    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal;
+    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal || MASK == kMaskVarlen, VARLEN = MASK == kMaskVarlen;
     typedef typename Frag8<T>::type F8;
     typedef typename Frag8<T>::half F4;
     constexpr int KROW = kBN * 2;       // K image: [D][64 keys], 128-B rows, 32-B chunk XOR swizzle
@@ -167,6 +203,18 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic(FwdParams p) {
     const T* __restrict__ Kb = (const T*)p.K + (int64_t)b * Nk * d;
     const T* __restrict__ Vb = (const T*)p.V + (int64_t)b * Nk * dv;
     const bool fast = p.fast != 0;
+    // the slab's extents in every bound below (VARLEN: per slab, varlen_ntiles' comment; N and Nk
+    // stay the strides); a workgroup with no query, or whose queries see no key, stores the
+    // empty-row state and leaves before any load or barrier (block-uniform)
+    VarlenExt ve{};
+    if constexpr (VARLEN) {
+        ve = varlen_extents(fwd_q_lens(p), fwd_k_lens(p), b, N, Nk, p.wleft, p.wright);
+        if (qb * kBM >= ve.nq || local_tile0(qb * kBM, ve.off, ve.left, kBN) >=
+                                     varlen_ntiles((ve.nk + kBN - 1) / kBN, qb * kBM + kBM - 1, ve.nq, ve.off, ve.right, kBN)) {
+            store_empty_rows<T>(p, b, qb * kBM, kBM, kThreads);
+            return;
+        }
+    }
 
     // Q^T fragments (B operand of S^T = K Q^T), kept in registers:
     // lane (r, h), k-step s holds Q[query qi][features 16s+8h .. 16s+8h+7].
@@ -228,13 +276,14 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic(FwdParams p) {
         }
     };
 
-    int ntiles = (Nk + kBN - 1) / kBN;
+    int ntiles = (FA_NKE + kBN - 1) / kBN;
     if constexpr (CAUSAL)   // tiles up to the block's last query's last visible key (causal_ntiles)
         ntiles = causal_ntiles(ntiles, qb * kBM + kBM - 1, N, (Nk - N), kBN);
     int jbeg = 0;
     if constexpr (LOCAL) {   // the tiles between the block's first query's left edge and its last query's right edge
-        jbeg = local_tile0(qb * kBM, Nk - N, p.wleft, kBN);
-        ntiles = local_ntiles(ntiles, qb * kBM + kBM - 1, N, Nk - N, p.wright, kBN);
+        jbeg = local_tile0(qb * kBM, FA_OFF, FA_WL, kBN);
+        if constexpr (VARLEN) ntiles = varlen_ntiles(ntiles, qb * kBM + kBM - 1, ve.nq, ve.off, ve.right, kBN);
+        else ntiles = local_ntiles(ntiles, qb * kBM + kBM - 1, N, Nk - N, p.wright, kBN);
     }
     gload(jbeg);
     lstore();
@@ -262,13 +311,13 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic(FwdParams p) {
 
         // ---- mask keys >= Nk (last tile only) ----
         const int key0 = j * kBN;
-        if (key0 + kBN > Nk) {
+        if (key0 + kBN > FA_NKE) {
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                 for (int x = 0; x < 16; ++x) {
                     const int kt = kb * 32 + (x & 3) + 4 * ((x >> 2) & 1) + 8 * h + 16 * (x >> 3);
-                    if (key0 + kt >= Nk) sacc[kb][x] = kNegInf;
+                    if (key0 + kt >= FA_NKE) sacc[kb][x] = kNegInf;
                 }
         }
         if constexpr (CAUSAL) {   // keys past the lane's query + off (tiles that straddle the wave's diagonal)
@@ -283,14 +332,14 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic(FwdParams p) {
             }
         }
         if constexpr (LOCAL) {   // after the ragged mask; only on tiles that straddle an edge of the wave's band
-            const int w0 = qb * kBM + wave * 32 + (Nk - N);
-            if (key0 + kBN - 1 > w0 + p.wright || key0 < w0 + 31 - p.wleft) {
+            const int w0 = qb * kBM + wave * 32 + FA_OFF;
+            if (key0 + kBN - 1 > w0 + FA_WR || key0 < w0 + 31 - FA_WL) {
 #pragma unroll
                 for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                     for (int x = 0; x < 16; ++x) {
                         const int kt = key0 + kb * 32 + (x & 3) + 4 * ((x >> 2) & 1) + 8 * h + 16 * (x >> 3);
-                        if (kt > qi + (Nk - N) + p.wright || kt < qi + (Nk - N) - p.wleft) sacc[kb][x] = kNegInf;
+                        if (kt > qi + FA_OFF + FA_WR || kt < qi + FA_OFF - FA_WL) sacc[kb][x] = kNegInf;
                     }
             }
         }
@@ -351,6 +400,24 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic(FwdParams p) {
     // ---- epilogue: O = O / l ; l, m in natural-log units ----
     const float lt = swap_halves_sum(l_run);
     const float inv = 1.0f / lt;
+    if constexpr (VARLEN) {   // a row past nq or without a key: O = 0, l = 0, m = -inf, by select
+        if (qi < N) {
+            const bool live = qi < ve.nq && lt > 0.0f;
+            T* Ob = (T*)p.O + (int64_t)b * N * dv;
+#pragma unroll
+            for (int cb = 0; cb < DV / 32; ++cb)
+#pragma unroll
+                for (int x = 0; x < 16; ++x) {
+                    const int cc = cb * 32 + acc_row(x, h);
+                    if (cc < dv) Ob[(int64_t)cc * N + qi] = live ? (T)(oacc[cb][x] * inv) : (T)0.0f;
+                }
+            if (h == 0) {
+                p.m[(int64_t)b * N + qi] = live ? m_run * p.scale : kNegInf;
+                p.l[(int64_t)b * N + qi] = live ? lt : 0.0f;
+            }
+        }
+        return;
+    }
     if (qi < N) {
         T* Ob = (T*)p.O + (int64_t)b * N * dv;
 #pragma unroll
@@ -372,7 +439,7 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic(FwdParams p) {
 // --------------------------------------------------------------------------
 template <int D, int DV, DenseMask MASK = kMaskNone>
 __global__ __launch_bounds__(kThreads) void dense_fwd_generic_f32(FwdParams p) {
-    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal;
+    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal || MASK == kMaskVarlen, VARLEN = MASK == kMaskVarlen;
     constexpr int KROWF = kBN;       // K image [D][64] floats
     constexpr int VROWF = kBN + 1;   // V image [DV][65] floats (pad → conflict-free column reads)
     constexpr int KCH = D * 16 / kThreads;
@@ -392,6 +459,18 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic_f32(FwdParams p) {
     const float* __restrict__ Kb = (const float*)p.K + (int64_t)b * Nk * d;
     const float* __restrict__ Vb = (const float*)p.V + (int64_t)b * Nk * dv;
     const bool fast = p.fast != 0;
+    // the slab's extents in every bound below (VARLEN: per slab, varlen_ntiles' comment; N and Nk
+    // stay the strides); a workgroup with no query, or whose queries see no key, stores the
+    // empty-row state and leaves before any load or barrier (block-uniform)
+    VarlenExt ve{};
+    if constexpr (VARLEN) {
+        ve = varlen_extents(fwd_q_lens(p), fwd_k_lens(p), b, N, Nk, p.wleft, p.wright);
+        if (qb * kBM >= ve.nq || local_tile0(qb * kBM, ve.off, ve.left, kBN) >=
+                                     varlen_ntiles((ve.nk + kBN - 1) / kBN, qb * kBM + kBM - 1, ve.nq, ve.off, ve.right, kBN)) {
+            store_empty_rows<float>(p, b, qb * kBM, kBM, kThreads);
+            return;
+        }
+    }
 
     const int qi = qb * kBM + wave * 32 + r;
     float qf[D / 2];  // lane (r, h), step t: Q[qi][feature 2t+h]
@@ -438,13 +517,14 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic_f32(FwdParams p) {
         }
     };
 
-    int ntiles = (Nk + kBN - 1) / kBN;
+    int ntiles = (FA_NKE + kBN - 1) / kBN;
     if constexpr (CAUSAL)   // tiles up to the block's last query's last visible key (causal_ntiles)
         ntiles = causal_ntiles(ntiles, qb * kBM + kBM - 1, N, (Nk - N), kBN);
     int jbeg = 0;
     if constexpr (LOCAL) {   // the tiles between the block's first query's left edge and its last query's right edge
-        jbeg = local_tile0(qb * kBM, Nk - N, p.wleft, kBN);
-        ntiles = local_ntiles(ntiles, qb * kBM + kBM - 1, N, Nk - N, p.wright, kBN);
+        jbeg = local_tile0(qb * kBM, FA_OFF, FA_WL, kBN);
+        if constexpr (VARLEN) ntiles = varlen_ntiles(ntiles, qb * kBM + kBM - 1, ve.nq, ve.off, ve.right, kBN);
+        else ntiles = local_ntiles(ntiles, qb * kBM + kBM - 1, N, Nk - N, p.wright, kBN);
     }
     gload(jbeg);
     lstore();
@@ -465,12 +545,12 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic_f32(FwdParams p) {
         }
 
         const int key0 = j * kBN;
-        if (key0 + kBN > Nk) {
+        if (key0 + kBN > FA_NKE) {
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                 for (int x = 0; x < 16; ++x)
-                    if (key0 + kb * 32 + acc_row(x, h) >= Nk) sacc[kb][x] = kNegInf;
+                    if (key0 + kb * 32 + acc_row(x, h) >= FA_NKE) sacc[kb][x] = kNegInf;
         }
         if constexpr (CAUSAL) {
             if (key0 + kBN - 1 > qb * kBM + wave * 32 + (Nk - N)) {
@@ -482,14 +562,14 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic_f32(FwdParams p) {
             }
         }
         if constexpr (LOCAL) {
-            const int w0 = qb * kBM + wave * 32 + (Nk - N);
-            if (key0 + kBN - 1 > w0 + p.wright || key0 < w0 + 31 - p.wleft) {
+            const int w0 = qb * kBM + wave * 32 + FA_OFF;
+            if (key0 + kBN - 1 > w0 + FA_WR || key0 < w0 + 31 - FA_WL) {
 #pragma unroll
                 for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                     for (int x = 0; x < 16; ++x) {
                         const int kt = key0 + kb * 32 + acc_row(x, h);
-                        if (kt > qi + (Nk - N) + p.wright || kt < qi + (Nk - N) - p.wleft) sacc[kb][x] = kNegInf;
+                        if (kt > qi + FA_OFF + FA_WR || kt < qi + FA_OFF - FA_WL) sacc[kb][x] = kNegInf;
                     }
             }
         }
@@ -545,6 +625,24 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic_f32(FwdParams p) {
 
     const float lt = swap_halves_sum(l_run);
     const float inv = 1.0f / lt;
+    if constexpr (VARLEN) {   // a row past nq or without a key: O = 0, l = 0, m = -inf, by select
+        if (qi < N) {
+            const bool live = qi < ve.nq && lt > 0.0f;
+            float* Ob = (float*)p.O + (int64_t)b * N * dv;
+#pragma unroll
+            for (int cb = 0; cb < DV / 32; ++cb)
+#pragma unroll
+                for (int x = 0; x < 16; ++x) {
+                    const int cc = cb * 32 + acc_row(x, h);
+                    if (cc < dv) Ob[(int64_t)cc * N + qi] = live ? (float)(oacc[cb][x] * inv) : (float)0.0f;
+                }
+            if (h == 0) {
+                p.m[(int64_t)b * N + qi] = live ? m_run * p.scale : kNegInf;
+                p.l[(int64_t)b * N + qi] = live ? lt : 0.0f;
+            }
+        }
+        return;
+    }
     if (qi < N) {
         float* Ob = (float*)p.O + (int64_t)b * N * dv;
 #pragma unroll
@@ -602,7 +700,7 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_generic_f32(FwdParams p) {
 // that does not move, and the exponent's offset is 0 while m_used = -inf (P = 0).
 template <class T, int D, int DV, int NW, int BN, int NQB, bool SPLIT = false, bool WIDE = false, DenseMask MASK = kMaskNone>
 __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
-    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal;
+    constexpr bool CAUSAL = MASK == kMaskCausal, LOCAL = MASK == kMaskLocal || MASK == kMaskVarlen, VARLEN = MASK == kMaskVarlen;
     static_assert(!(CAUSAL && SPLIT), "causal launches never split the keys");
     static_assert(!(LOCAL && SPLIT), "local launches never split the keys");
     typedef typename Frag8<T>::type F8;
@@ -660,6 +758,20 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
     const int N = p.N, Nk = p.Nk, d = p.d, dv = p.dv;
+    // the slab's extents in every bound below (VARLEN: the two lengths come by scalar loads, b is
+    // uniform; varlen_ntiles' comment).  A workgroup whose first row is >= nq, or whose tile range
+    // [jt0, jt1) is empty (none of its queries sees a key), stores the empty-row state of its
+    // rows below N and leaves here: before any K/V load, LDS store or barrier, block-uniformly, so
+    // the pipeline below always has a tile.
+    VarlenExt ve{};
+    if constexpr (VARLEN) {
+        ve = varlen_extents(fwd_q_lens(p), fwd_k_lens(p), b, N, Nk, p.wleft, p.wright);
+        if (qb * BM >= ve.nq || local_tile0(qb * BM, ve.off, ve.left, BN) >=
+                                    varlen_ntiles((ve.nk + BN - 1) / BN, qb * BM + BM - 1, ve.nq, ve.off, ve.right, BN)) {
+            store_empty_rows<T>(p, b, qb * BM, BM, NTH);
+            return;
+        }
+    }
     const auto qrs = slab_rsrc((const T*)p.Q + (int64_t)b * N * d, (uint32_t)(N * d * (int)sizeof(T)));
     const int ldk = p.ldk;
     const auto krs = slab_rsrc((const T*)p.K + (int64_t)b * ldk * d, (uint32_t)(ldk * d * (int)sizeof(T)));
@@ -681,15 +793,16 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
         const int ch = tid + NTH * it, f = ch / CPR, pc = ch % CPR;
         vgo[it] = vact ? (f * ldk + pc * 8) * 2 : 0x7FFFFFF0;
     }
-    const int NT = (Nk + BN - 1) / BN;
-    const bool ragged = (Nk % BN) != 0;
+    const int NT = (FA_NKE + BN - 1) / BN;
+    const bool ragged = (FA_NKE % BN) != 0;
     // key tiles [jt0, jt1) of this workgroup (all tiles unless split-KV)
     // (causal: up to the last tile any of the workgroup's queries sees)
     // (local: from the first query's left edge to the last query's right edge; jt0 < jt1)
-    const int jt0 = SPLIT ? split * p.tps : LOCAL ? local_tile0(qb * BM, Nk - N, p.wleft, BN) : 0;
+    const int jt0 = SPLIT ? split * p.tps : LOCAL ? local_tile0(qb * BM, FA_OFF, FA_WL, BN) : 0;
     int jt1 = SPLIT ? min(NT, jt0 + p.tps) : NT;
     if constexpr (CAUSAL) jt1 = causal_ntiles(NT, qb * BM + BM - 1, N, (Nk - N), BN);
-    if constexpr (LOCAL) jt1 = local_ntiles(NT, qb * BM + BM - 1, N, Nk - N, p.wright, BN);
+    if constexpr (LOCAL && !VARLEN) jt1 = local_ntiles(NT, qb * BM + BM - 1, N, Nk - N, p.wright, BN);
+    if constexpr (VARLEN) jt1 = varlen_ntiles(NT, qb * BM + BM - 1, ve.nq, ve.off, ve.right, BN);
 
     u32x4 kreg[KCH], vreg[VCH];
     auto gload = [&](int j) {
@@ -770,7 +883,7 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
 #pragma unroll
             for (int it = 0; it < VCH; ++it) {
                 const int ch = tid + NTH * it;
-                if (j * BN + (ch % CPR) * 8 >= Nk) vreg[it] = u32x4{0u, 0u, 0u, 0u};
+                if (j * BN + (ch % CPR) * 8 >= FA_NKE) vreg[it] = u32x4{0u, 0u, 0u, 0u};
             }
         }
 #pragma unroll
@@ -806,7 +919,7 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
 #pragma unroll
                     for (int x = 0; x < 16; ++x) {
                         const int kt = kb * 32 + (x & 3) + 4 * ((x >> 2) & 1) + 8 * h + 16 * (x >> 3);
-                        if (key0 + kt >= Nk) sacc[u][kb][x] = kNegInf;
+                        if (key0 + kt >= FA_NKE) sacc[u][kb][x] = kNegInf;
                     }
         }
         if constexpr (CAUSAL) {
@@ -835,11 +948,11 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
             // the same select on each side of the band: wr, wl are the right and left key limits of
             // the wave's first query relative to the tile (scalars); the lane term is rebuilt from
             // the lane id inside each branch, so no mask register lives across the loop
-            const int wf = qb * BM + __builtin_amdgcn_readfirstlane(wave) * NQB * 32 + (Nk - N) - j * BN;
-            const int wr = wf + p.wright, wl = wf - p.wleft;
-            if (BN - 1 > wr) {   // a key past the first query's right limit
+            const int wf = qb * BM + __builtin_amdgcn_readfirstlane(wave) * NQB * 32 + FA_OFF - j * BN;
+            const int wrt = wf + FA_WR, wlt = wf - FA_WL;
+            if (BN - 1 > wrt) {   // a key past the first query's right limit
                 const int ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-                const int lr = (ln & 31) - 8 * (ln >> 5) + wr;
+                const int lr = (ln & 31) - 8 * (ln >> 5) + wrt;
 #pragma unroll
                 for (int u = 0; u < NQB; ++u)
 #pragma unroll
@@ -850,9 +963,9 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
                             if (ktc > lr) sacc[u][kb][x] = kNegInf;
                         }
             }
-            if (wl + NQB * 32 - 1 > 0) {   // a key before the last query's left limit
+            if (wlt + NQB * 32 - 1 > 0) {   // a key before the last query's left limit
                 const int ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-                const int ll = (ln & 31) - 8 * (ln >> 5) + wl;
+                const int ll = (ln & 31) - 8 * (ln >> 5) + wlt;
 #pragma unroll
                 for (int u = 0; u < NQB; ++u)
 #pragma unroll
@@ -951,8 +1064,11 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
     if constexpr (CAUSAL) wlast = qb * BM + (__builtin_amdgcn_readfirstlane(wave) + 1) * NQB * 32 - 1 + (Nk - N);
     int wlo = 0, whi = 0;   // local: the first key of the wave's first query and the last key of its last query, scalars
     if constexpr (LOCAL) {
-        wlo = qb * BM + __builtin_amdgcn_readfirstlane(wave) * NQB * 32 + (Nk - N) - p.wleft;
-        whi = qb * BM + (__builtin_amdgcn_readfirstlane(wave) + 1) * NQB * 32 - 1 + (Nk - N) + p.wright;
+        wlo = qb * BM + __builtin_amdgcn_readfirstlane(wave) * NQB * 32 + FA_OFF - FA_WL;
+        whi = qb * BM + (__builtin_amdgcn_readfirstlane(wave) + 1) * NQB * 32 - 1 + FA_OFF + FA_WR;
+        if constexpr (VARLEN) {   // a wave whose rows are all past nq computes no tile
+            if (qb * BM + __builtin_amdgcn_readfirstlane(wave) * NQB * 32 >= ve.nq) whi = -0x40000000;
+        }
     }
     for (int j = jt0; j < jt1; j += 2) {
         gload(min(j + 1, jt1 - 1));
@@ -1021,7 +1137,19 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
         for (int u = 0; u < NQB; ++u) {
             const int qi = qiv[u];
             const float lt = swap_halves_sum(l_run[u]);
-            const float inv = 1.0f / lt;
+            float inv = 1.0f / lt;
+            // VARLEN: a row past nq or without a key leaves as O = 0, l = 0, m = -inf, by select
+            // (its accumulators are zeroed first: 0 * inv = +0 whatever their sign was)
+            if constexpr (VARLEN) {
+                const bool live = qi < ve.nq && lt > 0.0f;
+                inv = live ? inv : 0.0f;
+                m_true[u] = live ? m_true[u] : kNegInf;   // m = -inf * scale; l below: 0 * 2^(...) needs its own select
+                l_run[u] = live ? 1.0f : 0.0f;            // (reused as the row's live flag from here on)
+#pragma unroll
+                for (int cb = 0; cb < DV / 32; ++cb)
+#pragma unroll
+                    for (int x = 0; x < 16; ++x) oacc[u][cb][x] = live ? oacc[u][cb][x] : 0.0f;
+            }
             const int tb = ((wave * NQB + u) * 32 + (r & ~1)) * 2;
             // acc_row(4 k + e, h) = 8 k + e + 4 h (e = 0, 1); + 2 for register 4 k + e + 2
             const int wb[2] = {qo_at(4 * h + 2 * odd, tb), qo_at(4 * h + 2 * odd + 1, tb)};
@@ -1038,8 +1166,13 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
                             __builtin_amdgcn_perm((unsigned)nb, (unsigned)ow, sel);
                     }
             if (qi < N && h == 0) {
-                p.m[(int64_t)b * N + qi] = m_true[u] * p.scale;
-                p.l[(int64_t)b * N + qi] = lt * exp2_fast((m_used[u] - m_true[u]) * c);
+                if constexpr (VARLEN) {
+                    p.m[(int64_t)b * N + qi] = m_true[u] * p.scale;
+                    p.l[(int64_t)b * N + qi] = l_run[u] != 0.0f ? lt * exp2_fast((m_used[u] - m_true[u]) * c) : 0.0f;
+                } else {
+                    p.m[(int64_t)b * N + qi] = m_true[u] * p.scale;
+                    p.l[(int64_t)b * N + qi] = lt * exp2_fast((m_used[u] - m_true[u]) * c);
+                }
             }
         }
         FA_FWD_STAMP(8);
@@ -1076,7 +1209,17 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
     for (int u = 0; u < NQB; ++u) {
         const int qi = qiv[u];
         const float lt = swap_halves_sum(l_run[u]);
-        const float inv = 1.0f / lt;
+        float inv = 1.0f / lt;
+        if constexpr (VARLEN) {   // as in the WIDE epilogue above
+            const bool live = qi < ve.nq && lt > 0.0f;
+            inv = live ? inv : 0.0f;
+            m_true[u] = live ? m_true[u] : kNegInf;
+            l_run[u] = live ? 1.0f : 0.0f;
+#pragma unroll
+            for (int cb = 0; cb < DV / 32; ++cb)
+#pragma unroll
+                for (int x = 0; x < 16; ++x) oacc[u][cb][x] = live ? oacc[u][cb][x] : 0.0f;
+        }
         if (qi < N) {
             T* Ob = (T*)p.O + (int64_t)b * N * dv;
 #pragma unroll
@@ -1087,12 +1230,22 @@ __device__ __forceinline__ void dense_fwd_tiled(const FwdParams& p) {
                     if (cc < dv) Ob[(int64_t)cc * N + qi] = (T)(oacc[u][cb][x] * inv);
                 }
             if (h == 0) {
-                p.m[(int64_t)b * N + qi] = m_true[u] * p.scale;
-                p.l[(int64_t)b * N + qi] = lt * exp2_fast((m_used[u] - m_true[u]) * c);
+                if constexpr (VARLEN) {
+                    p.m[(int64_t)b * N + qi] = m_true[u] * p.scale;
+                    p.l[(int64_t)b * N + qi] = l_run[u] != 0.0f ? lt * exp2_fast((m_used[u] - m_true[u]) * c) : 0.0f;
+                } else {
+                    p.m[(int64_t)b * N + qi] = m_true[u] * p.scale;
+                    p.l[(int64_t)b * N + qi] = lt * exp2_fast((m_used[u] - m_true[u]) * c);
+                }
             }
         }
     }
 }
+
+#undef FA_NKE
+#undef FA_OFF
+#undef FA_WL
+#undef FA_WR
 
 // the four default geometries under a mask (a masked launch never splits, never runs fa_fwd_p4)
 template <class T, int D, int DV, DenseMask MASK = kMaskNone>
@@ -1265,10 +1418,14 @@ int launch_dense_fwd(const DenseArgs& a, hipStream_t s, const char** why) {
     p.rescale_log2 = g_fwd_rescale_log2;
     p.batch = (int)a.batch;
     p.nsplit = pl.nsplit; p.tps = pl.tps; p.opart = p.lpart = p.mpart = nullptr;
-    if (a.mask == kMaskLocal) {   // never split: the window rides in the split's two ints (fa_fwd_params.h)
+    if (a.mask == kMaskLocal || a.mask == kMaskVarlen) {   // never split: the window rides in the split's two ints (fa_fwd_params.h)
         const MaskInts mi = mask_ints(a.mask, a.left, a.right, a.N, a.Nk);
         p.wleft = mi.left;
         p.wright = mi.right;
+    }
+    if (a.mask == kMaskVarlen) {   // ... and the lengths in its first two partial pointers (fwd_q_lens, fwd_k_lens)
+        p.opart = (float*)a.q_lens;
+        p.lpart = (float*)a.k_lens;
     }
     p.causal = pl.causal;
     p.fast = pl.kv_vec;

@@ -29,6 +29,10 @@ struct FwdParams {
     union { int nsplit; int wleft; };
     union { int tps; int wright; };
     int batch;
+    // Varlen launches (fa_varlen_fwd) never split either: their two length arrays (device
+    // pointers to `batch` int32, null = full) ride in the first two partial pointers, opart and
+    // lpart, and are read through fwd_q_lens / fwd_k_lens by the kMaskVarlen instantiations only.
+    // (A cast at the two accessors, not a union: a union member changes the split kernels' code.)
     float *opart, *lpart, *mpart;
     float scale, scale_log2;
     float rescale_log2;   // lazy-rescale threshold (log2 units): kRescaleLog2, or the debug knob
@@ -41,6 +45,8 @@ struct FwdParams {
     // padding: sizeof(FwdParams) and every existing kernel's argument layout stay as they were.
     int causal = 0;
 };
+__host__ __device__ inline const int32_t* fwd_q_lens(const FwdParams& p) { return (const int32_t*)p.opart; }
+__host__ __device__ inline const int32_t* fwd_k_lens(const FwdParams& p) { return (const int32_t*)p.lpart; }
 static_assert(sizeof(FwdParams) == 136, "fwd_split_combine's second argument follows the struct: keep its size");
 
 }  // namespace fa

@@ -14,7 +14,9 @@ namespace fa {
 // three masks).  ONE value travels from the extern "C" entry points (api.cpp) through
 // DenseArgs / DenseBwdArgs and the plans (fa_dense_plan.h) to the kernels' single MASK
 // template parameter, which by_mask below turns into a compile-time constant.
-enum DenseMask : int { kMaskNone = 0, kMaskCausal = 1, kMaskLocal = 2 };
+// kMaskVarlen (fa_varlen_fwd / fa_varlen_bwd) is the local mask with per-slab extents: the
+// kernels read q_lens[b], k_lens[b] and run the local bodies on the leading (nq, nk) rows.
+enum DenseMask : int { kMaskNone = 0, kMaskCausal = 1, kMaskLocal = 2, kMaskVarlen = 3 };
 
 struct DenseArgs {
     int dtype;                 // fa_dtype
@@ -31,6 +33,9 @@ struct DenseArgs {
     // (mask_ints clamps).  left / right are read under kMaskLocal only.
     DenseMask mask = kMaskNone;
     int64_t left = -1, right = -1;
+    // kMaskVarlen only: device pointers to `batch` int32 lengths (nullptr: every slab is full on
+    // that side); clamped on the device (varlen_clamp), never read on the host
+    const int32_t *q_lens = nullptr, *k_lens = nullptr;
 };
 
 struct DenseBwdArgs {
@@ -45,6 +50,7 @@ struct DenseBwdArgs {
     double scale64 = 0.0;      // Float64 kernels: τ resolved in double (0: use scale)
     DenseMask mask = kMaskNone;   // as DenseArgs::mask (a masked backward is always the two-pass form)
     int64_t left = -1, right = -1;
+    const int32_t *q_lens = nullptr, *k_lens = nullptr;   // as DenseArgs (kMaskVarlen only)
 };
 
 struct WindowGeom {
@@ -176,18 +182,27 @@ inline int head_dim_class(int64_t d) {
 constexpr int kMaxHeadDim = 128;
 
 // "causal" / "local": the mask's word in messages and entry-point names ("dense" for kMaskNone)
-inline const char* mask_word(DenseMask mask) { return mask == kMaskLocal ? "local" : mask == kMaskCausal ? "causal" : "dense"; }
+inline const char* mask_word(DenseMask mask) {
+    return mask == kMaskVarlen ? "varlen" : mask == kMaskLocal ? "local" : mask == kMaskCausal ? "causal" : "dense";
+}
 // A masked call needs Nk >= N: true, with the mask's message in *why, when it has fewer keys.
 inline bool mask_lacks_keys(DenseMask mask, int64_t N, int64_t Nk, const char** why) {
     if (mask == kMaskNone || Nk >= N) return false;
-    *why = mask == kMaskLocal ? "local attention needs Nk >= N (a query would see no key)"
-                              : "causal attention needs Nk >= N (a query would see no key)";
+    *why = mask == kMaskVarlen  ? "varlen attention needs Nk >= N (a query would see no key)"
+           : mask == kMaskLocal ? "local attention needs Nk >= N (a query would see no key)"
+                                : "causal attention needs Nk >= N (a query would see no key)";
     return true;
 }
 // The mask as the five ints of the device parameter structs (BwdParams, F64Params; FwdParams
 // takes the window only).  off = Nk - N of the caller's extents.  A side of the local window
 // lands in [0, Nk], where Nk binds nowhere (negative = unbounded, and a value >= Nk is the
 // same), clamped on the 64-bit value before it becomes a 32-bit int.
+// kMaskVarlen: off is per slab (nk - nq, anywhere in [-N, Nk]) and the kernels compute it; `off`
+// here stays 0.  Nk as "no bound" relies on off >= 0 (i + off + Nk >= Nk), so the varlen window
+// is clamped in two steps that bind nowhere for any off: here left to [0, Nk] and right to
+// [0, N], and per slab (varlen_extents) left to nk and right to nq.  For a query i < nq,
+// i + off - nk = i - nq < 0 and i + off + nq = i + nk >= nk; and i + off + right <= nk + nq
+// stays a 32-bit int.
 struct MaskInts {
     int causal = 0, off = 0, local = 0, left = 0, right = 0;
 };
@@ -201,7 +216,34 @@ inline MaskInts mask_ints(DenseMask mask, int64_t left, int64_t right, int64_t N
         r.left = (int)(left < 0 || left > Nk ? Nk : left);
         r.right = (int)(right < 0 || right > Nk ? Nk : right);
     }
+    if (mask == kMaskVarlen) {
+        r.off = 0;
+        r.local = 1;
+        r.left = (int)(left < 0 || left > Nk ? Nk : left);
+        r.right = (int)(right < 0 || right > N ? N : right);
+    }
     return r;
+}
+
+// A caller's length as the kernels use it: clamped to [0, n].  Lengths are device data and the
+// ABI does not synchronise, so this clamp, not a host check, is what keeps every index in
+// bounds (fa_debug_varlen_clamp exposes it to the host tests).
+__host__ __device__ inline int varlen_clamp(int len, int n) { return len < 0 ? 0 : len > n ? n : len; }
+// The extents of slab b under kMaskVarlen: the leading nq queries and nk keys (N, Nk: the
+// caller's extents; a null array means full), off = nk - nq, and the window with each side
+// clamped where it binds nowhere (mask_ints).
+struct VarlenExt {
+    int nq, nk, off, left, right;
+};
+__host__ __device__ inline VarlenExt varlen_extents(const int32_t* q_lens, const int32_t* k_lens, int b, int N, int Nk,
+                                                    int left, int right) {
+    VarlenExt e;
+    e.nq = q_lens ? varlen_clamp(q_lens[b], N) : N;
+    e.nk = k_lens ? varlen_clamp(k_lens[b], Nk) : Nk;
+    e.off = e.nk - e.nq;
+    e.left = left < e.nk ? left : e.nk;
+    e.right = right < e.nq ? right : e.nq;
+    return e;
 }
 
 // Workspace regions start on 256-B boundaries; the vector paths want 16-B aligned tensors.
@@ -233,6 +275,7 @@ inline bool by_mask(DenseMask mask, F&& f) {
         case kMaskNone: f(mask_c<kMaskNone>{}); return true;
         case kMaskCausal: f(mask_c<kMaskCausal>{}); return true;
         case kMaskLocal: f(mask_c<kMaskLocal>{}); return true;
+        case kMaskVarlen: f(mask_c<kMaskVarlen>{}); return true;
     }
     return false;
 }

@@ -43,6 +43,7 @@ __all__ = [
     "circulant_dpa",
     "causal_fa", "causal_fa_", "causal_fa_backward", "causal_dpa",
     "local_fa", "local_fa_", "local_fa_backward", "local_dpa",
+    "varlen_fa", "varlen_fa_", "varlen_fa_backward", "varlen_dpa",
     "fused_softmax", "fused_softmax_", "DTYPES",
 ]
 
@@ -171,6 +172,24 @@ def lib() -> ctypes.CDLL:
         L.fa_debug_local_bwd_plan.restype = ctypes.c_int
         L.fa_debug_local_bwd_plan.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64, ctypes.c_int,
                                               ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(i64)]
+    if hasattr(L, "fa_varlen_fwd"):
+        for wq in (L.fa_varlen_fwd_workspace, L.fa_varlen_bwd_workspace):
+            wq.restype = ctypes.c_size_t
+            wq.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64]
+        L.fa_varlen_fwd.restype = ctypes.c_int
+        L.fa_varlen_fwd.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, vp, vp, i64, i64, f32,
+                                    vp, ctypes.c_size_t, vp]
+        L.fa_varlen_bwd.restype = ctypes.c_int
+        L.fa_varlen_bwd.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                    i64, i64, i64, i64, i64, vp, vp, i64, i64, f32, vp, ctypes.c_size_t, vp]
+        L.fa_debug_varlen_fwd_plan.restype = ctypes.c_int
+        L.fa_debug_varlen_fwd_plan.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(i64)]
+        L.fa_debug_varlen_bwd_plan.restype = ctypes.c_int
+        L.fa_debug_varlen_bwd_plan.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64, ctypes.c_int,
+                                               ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(i64)]
+        L.fa_debug_varlen_clamp.restype = ctypes.c_int
+        L.fa_debug_varlen_clamp.argtypes = [ctypes.c_int, ctypes.c_int]
     L.fa_softmax_workspace.restype = ctypes.c_size_t
     L.fa_softmax_workspace.argtypes = [i64, i64, i64, ctypes.c_int]
     L.fa_softmax.restype = ctypes.c_int
@@ -343,14 +362,19 @@ def dense_fa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float = 0
 
 # ----------------------------------------------------------------------------
 # causal and local (sliding window around the causal diagonal) dense attention: one
-# implementation each, parameterised by the mask's name ("causal" / "local", as in the C
-# ABI's fa_<mask>_fwd ...) and its window: () for causal, (left, right) for local
+# implementation each, parameterised by the mask's name ("causal" / "local" / "varlen", as in the
+# C ABI's fa_<mask>_fwd ...) and the arguments between `batch` and `scale`: () for causal,
+# (left, right) for local, (q_lens, k_lens, left, right) for varlen (the lengths as pointers)
 # ----------------------------------------------------------------------------
 def _masked_extents(mask: str, N: int, Nk: int) -> None:
     """The C ABI's rule, raised before any device is touched."""
     if Nk < N:
         raise FlashAttentionError(FA_ERR_UNSUPPORTED,
                                   f"{mask} attention needs Nk >= N (got N = {N}, Nk = {Nk}): a query would see no key")
+
+
+def _mask_args(window):
+    return [w if isinstance(w, ctypes.c_void_p) else int(w) for w in window]
 
 
 def _masked_fa_(mask: str, window: Tuple[int, ...], O, l, m, Q, K, V, scale: float):
@@ -370,7 +394,7 @@ def _masked_fa_(mask: str, window: Tuple[int, ...], O, l, m, Q, K, V, scale: flo
     nws = getattr(Lb, f"fa_{mask}_fwd_workspace")(code, N, Nk, d, dv, B)
     ws = _workspace(Q.device, nws) if nws else None
     _check(getattr(Lb, f"fa_{mask}_fwd")(code, _ptr(Q), _ptr(K), _ptr(V), _ptr(O), _ptr(l), _ptr(m),
-                                         N, Nk, d, dv, B, *map(int, window), float(scale), _ptr(ws), int(nws), _stream(Q)))
+                                         N, Nk, d, dv, B, *_mask_args(window), float(scale), _ptr(ws), int(nws), _stream(Q)))
     return O, l, m
 
 
@@ -402,7 +426,7 @@ def _masked_fa_backward(mask: str, window: Tuple[int, ...], Q, K, V, O, dO, l, m
     nws = getattr(L, f"fa_{mask}_bwd_workspace")(code, N, Nk, d, dv, B)
     ws = _workspace(Q.device, nws, entry=f"{mask}_fa_backward")
     _check(getattr(L, f"fa_{mask}_bwd")(code, _ptr(Q), _ptr(K), _ptr(V), _ptr(O), _ptr(dO), _ptr(l), _ptr(m),
-                                        _ptr(dQ), _ptr(dK), _ptr(dV), N, Nk, d, dv, B, *map(int, window), float(scale),
+                                        _ptr(dQ), _ptr(dK), _ptr(dV), N, Nk, d, dv, B, *_mask_args(window), float(scale),
                                         _ptr(ws), int(nws), _stream(Q)))
     return dQ, dK, dV
 
@@ -498,6 +522,115 @@ def local_dpa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, left: int, righ
     P = softmax over the keys by this library's fa_softmax kernel (dims = 2; exactly 0 outside
     the window), O = P V.  P is (N, Nk, B) in the input dtype; memory is O(N·Nk·B)."""
     return _masked_dpa("local", left, right, q, k, v, scale)
+
+
+# ----------------------------------------------------------------------------
+# varlen: per-sequence lengths in a padded batch (fa_varlen_fwd / fa_varlen_bwd)
+# ----------------------------------------------------------------------------
+def _lens(lens, n: int, B: int, device, name: str) -> Optional[torch.Tensor]:
+    """A lengths argument as the C ABI takes it: None (every slab full), or an int32 device
+    tensor of shape (B,).  A device tensor is passed as it is (the kernels clamp it; nothing is
+    read back).  A host sequence or CPU tensor is range-checked against [0, n] here
+    (DimensionMismatch) and copied to the device."""
+    if lens is None:
+        return None
+    if isinstance(lens, torch.Tensor) and lens.device.type == "cuda":
+        _require(lens.dtype == torch.int32 and tuple(lens.shape) == (B,) and lens.is_contiguous(),
+                 f"DimensionMismatch: {name} must be a contiguous int32 tensor of shape ({B},)")
+        _require(lens.device == device, "arrays on different devices")
+        return lens
+    host = torch.as_tensor(lens, device="cpu")
+    _require(host.dim() == 1 and host.numel() == B and not host.is_floating_point() and host.dtype != torch.bool,
+             f"DimensionMismatch: {name} must hold {B} integer lengths")
+    host = host.to(torch.int64)
+    _require(bool(((host >= 0) & (host <= n)).all()), f"DimensionMismatch: {name} must lie in [0, {n}]")
+    return host.to(torch.int32).to(device)
+
+
+def varlen_fa_(O: torch.Tensor, l: torch.Tensor, m: torch.Tensor,
+               Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor,
+               q_lens=None, k_lens=None, left: int = -1, right: int = -1,
+               scale: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """:func:`local_fa_` with per-slab lengths, in place.  Slab b is the leading
+    nq = q_lens[b] queries and nk = k_lens[b] keys of its (N, Nk) slab; with off = nk - nq
+    (of either sign) query i < nq attends the keys 0 <= j < nk with
+    i + off - left <= j <= i + off + right (a negative side unbounded): (-1, -1) is a
+    key-padding mask, (-1, 0) causal per sequence, bottom-right aligned.  Rows i >= nq and queries
+    that see no key get O = 0, l = 0, m = -Inf.  Padding rows of Q, K, V may hold anything finite.
+    Lengths: None (full), an int32 device tensor of shape (B,), or a host sequence / CPU tensor
+    (checked against [0, N] / [0, Nk], then copied).  Nk < N raises FlashAttentionError."""
+    _require(Q.dim() == 3 and K.dim() == 3, "varlen_fa! expects 3-D (N, d, batch) arrays")
+    ql = _lens(q_lens, Q.shape[0], Q.shape[2], Q.device, "q_lens")
+    kl = _lens(k_lens, K.shape[0], Q.shape[2], Q.device, "k_lens")
+    return _masked_fa_("varlen", (_ptr(ql), _ptr(kl), left, right), O, l, m, Q, K, V, scale)
+
+
+def varlen_fa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_lens=None, k_lens=None,
+              left: int = -1, right: int = -1, scale: float = 0.0):
+    """``varlen_fa(q, k, v, q_lens, k_lens, left, right) -> (O, l, m)``: :func:`varlen_fa_` on
+    fresh outputs.  q (N, d, B), k (Nk, d, B), v (Nk, dv, B) with Nk >= N."""
+    _require(q.dim() == 3 and k.dim() == 3, "varlen_fa expects 3-D (N, d, batch) arrays")
+    ql = _lens(q_lens, q.shape[0], q.shape[2], q.device, "q_lens")
+    kl = _lens(k_lens, k.shape[0], q.shape[2], q.device, "k_lens")
+    return _masked_fa("varlen", (_ptr(ql), _ptr(kl), left, right), q, k, v, scale)
+
+
+def varlen_fa_backward(Q, K, V, O, dO, l, m, q_lens=None, k_lens=None, left: int = -1, right: int = -1,
+                       scale: float = 0.0):
+    """Backward of :func:`varlen_fa` for the same lengths and window: ``(dQ, dK, dV)``.  O, l, m
+    are the forward's outputs.  Always the two-pass form: all three gradients are bitwise
+    reproducible.  dQ rows i >= nq, dK / dV rows j >= nk, and the rows of queries and keys that
+    see nothing are exact zeros; padding rows of Q, K, V, dO may hold anything finite."""
+    _require(Q.dim() == 3 and K.dim() == 3, "varlen_fa_backward expects 3-D (N, d, batch) arrays")
+    ql = _lens(q_lens, Q.shape[0], Q.shape[2], Q.device, "q_lens")
+    kl = _lens(k_lens, K.shape[0], Q.shape[2], Q.device, "k_lens")
+    return _masked_fa_backward("varlen", (_ptr(ql), _ptr(kl), left, right), Q, K, V, O, dO, l, m, scale)
+
+
+def varlen_dpa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_lens=None, k_lens=None,
+               left: int = -1, right: int = -1, scale: float = 0.0):
+    """``varlen_dpa(...) -> (O, l, m)``: the naive form of :func:`varlen_fa` from torch ops with
+    an explicit (N, Nk, B) mask, in :func:`local_dpa`'s spirit: S = τ Q Kᵀ by a library GEMM in
+    float32, −∞ where the key is hidden, m = max, l = Σ exp(S − m), O = (exp(S − m) V) / l.  A row
+    with no visible key returns the empty-row state O = 0, l = 0, m = −Inf.  Memory is O(N·Nk·B)."""
+    _require(q.dim() == 3 and k.dim() == 3 and v.dim() == 3, "varlen_dpa expects 3-D (N, d, batch) arrays")
+    N, d, B = q.shape
+    Nk, dv = k.shape[0], v.shape[1]
+    _require(k.shape == (Nk, d, B) and v.shape == (Nk, dv, B),
+             "DimensionMismatch: k must match q's feature and batch dims, v k's token count and the batch dim")
+    dev = q.device
+    ql = _lens(q_lens, N, B, dev, "q_lens")
+    kl = _lens(k_lens, Nk, B, dev, "k_lens")
+    _dtype_code(q, k, v)
+    _masked_extents("varlen", N, Nk)
+    _device_check(q, k, v)
+    nq = (torch.full((B,), N, device=dev) if ql is None else ql.clamp(0, N)).long()[:, None, None]
+    nk = (torch.full((B,), Nk, device=dev) if kl is None else kl.clamp(0, Nk)).long()[:, None, None]
+    tau = float(scale) if scale > 0 else 1.0 / math.sqrt(d)
+    acc = torch.float64 if q.dtype == torch.float64 else torch.float32
+    Qr, Kr, Vr = _rm(q).to(acc), _rm(k).to(acc), _rm(v).to(acc)    # [B][d][N], [B][d][Nk], [B][dv][Nk]
+    S = torch.bmm(Qr.transpose(1, 2), Kr) * tau                    # [B][N][Nk]
+    i = torch.arange(N, device=dev)[None, :, None]
+    j = torch.arange(Nk, device=dev)[None, None, :]
+    c = i + (nk - nq)
+    vis = (i < nq) & (j < nk)
+    if right >= 0:
+        vis &= j <= c + int(right)
+    if left >= 0:
+        vis &= j >= c - int(left)
+    S = S.masked_fill(~vis, float("-inf"))
+    mx = S.max(dim=2, keepdim=True).values                          # -inf on an empty row
+    E = torch.exp(S - torch.where(torch.isinf(mx), torch.zeros_like(mx), mx))   # 0 on an empty row
+    ls = E.sum(dim=2, keepdim=True)
+    Or = torch.bmm(E, Vr.transpose(1, 2))                           # [B][N][dv]; a hidden key's V meets E = 0
+    Or = torch.where(ls > 0, Or / torch.where(ls > 0, ls, torch.ones_like(ls)), torch.zeros_like(Or))
+    O = jl_empty((N, dv, B), q.dtype, dev)
+    O.copy_(Or.permute(1, 2, 0))
+    l = jl_empty((N, 1, B), torch.float32, dev)
+    m = jl_empty((N, 1, B), torch.float32, dev)
+    l.copy_(ls.permute(1, 2, 0))
+    m.copy_(mx.permute(1, 2, 0))
+    return O, l, m
 
 
 def circulant_fa_(O: torch.Tensor, l: torch.Tensor, m: torch.Tensor,
@@ -635,7 +768,7 @@ def backward_handoff_status(device=None) -> int:
     stream = torch.cuda.current_stream(device)
     key = (device.type, device.index, stream.cuda_stream)
     buf = _WS.get(key)
-    _require(buf is not None and _WS_LAST.get(key) in ("dense_fa_backward", "causal_fa_backward", "local_fa_backward"),
+    _require(buf is not None and _WS_LAST.get(key) in ("dense_fa_backward", "causal_fa_backward", "local_fa_backward", "varlen_fa_backward"),
              "the last call that used this stream's scratch buffer was not dense_fa_backward")
     st = ctypes.c_int(-2)
     _check(lib().fa_dense_bwd_handoff_status(_ptr(buf), buf.numel(), ctypes.c_void_p(stream.cuda_stream),

@@ -467,6 +467,78 @@ function local_fa_backward(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3},
     return local_fa_backward_f32(Q, K, V, O, dO, Float32.(l), Float32.(m), left, right)
 end
 
+# varlen_fa!(O, l, m, Q, K, V; q_lens, k_lens, left, right) — local_fa! with per-slab lengths in a
+# padded batch (the reference has none).  q_lens, k_lens: ROCArray{Int32,1} of length B, or
+# `nothing` (every slab full on that side).  Slab b is its leading nq = q_lens[b] queries and
+# nk = k_lens[b] keys; with off = nk - nq query i < nq attends 0 <= j < nk,
+# i + off - left <= j <= i + off + right (a negative side unbounded).  Rows past nq and queries
+# that see no key get O = 0, l = 0, m = -Inf.  Lengths are clamped on the device, never read here.
+lens_ptr(::Nothing, B) = Ptr{Cint}(C_NULL)
+function lens_ptr(x::ROCArray{Int32,1}, B)
+    length(x) == B || throw(DimensionMismatch("lengths must have one entry per batch slab"))
+    return Base.unsafe_convert(Ptr{Cint}, pointer(x))
+end
+
+function varlen_fa!(O::ROCArray{T,3}, l::ROCArray{Float32,3}, m::ROCArray{Float32,3},
+                    Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3};
+                    q_lens=nothing, k_lens=nothing, left::Integer=-1, right::Integer=-1) where {T}
+    N, d, B = size(Q)
+    Nk, dv = size(K, 1), size(V, 2)
+    size(K) == (Nk, d, B) || throw(DimensionMismatch("K"))
+    size(V) == (Nk, dv, B) || throw(DimensionMismatch("V"))
+    size(O) == (N, dv, B) || throw(DimensionMismatch("O"))
+    size(l) == (N, 1, B) && size(m) == (N, 1, B) || throw(DimensionMismatch("l, m must be (N, 1, batch)"))
+    nws = ccall((:fa_varlen_fwd_workspace, libfa_hip), Csize_t,
+                (Cint, Int64, Int64, Int64, Int64, Int64), fa_dtype(T), N, Nk, d, dv, B)
+    GC.@preserve q_lens k_lens with_workspace(nws) do ws
+        fa_check(ccall((:fa_varlen_fwd, libfa_hip), Cint,
+                       (Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32},
+                        Int64, Int64, Int64, Int64, Int64, Ptr{Cint}, Ptr{Cint}, Int64, Int64, Cfloat,
+                        Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+                       fa_dtype(T), Q, K, V, O, l, m, N, Nk, d, dv, B, lens_ptr(q_lens, B), lens_ptr(k_lens, B),
+                       Int64(left), Int64(right), 0f0, ws, nws, stream_ptr()))
+    end
+    return O, l, m
+end
+
+# varlen_fa(Q, K, V; q_lens, k_lens, left, right) -> (O, l, m), Float32 statistics
+function varlen_fa(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3}; kw...) where {T}
+    N, B = size(Q, 1), size(Q, 3)
+    O = similar(Q, N, size(V, 2), B)
+    l = similar(Q, Float32, N, 1, B)
+    m = similar(Q, Float32, N, 1, B)
+    return varlen_fa!(O, l, m, Q, K, V; kw...)
+end
+
+# varlen_fa_backward(Q, K, V, O, dO, l, m; q_lens, k_lens, left, right) -> (dQ, dK, dV): the
+# two-pass form, bitwise reproducible; exact zeros past the lengths and on empty rows
+function varlen_fa_backward(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3},
+                            O::ROCArray{T,3}, dO::ROCArray{T,3},
+                            l::ROCArray{Float32,3}, m::ROCArray{Float32,3};
+                            q_lens=nothing, k_lens=nothing, left::Integer=-1, right::Integer=-1) where {T}
+    N, d, B = size(Q)
+    Nk, dv = size(K, 1), size(V, 2)
+    size(K) == (Nk, d, B) && size(V) == (Nk, dv, B) ||
+        throw(DimensionMismatch("K, V shapes disagree with Q"))
+    size(O) == (N, dv, B) && size(dO) == (N, dv, B) ||
+        throw(DimensionMismatch("O, dO must be (N, dv, batch)"))
+    size(l) == (N, 1, B) && size(m) == (N, 1, B) ||
+        throw(DimensionMismatch("l, m must be (N, 1, batch)"))
+    dQ, dK, dV = similar(Q), similar(K), similar(V)
+    nws = ccall((:fa_varlen_bwd_workspace, libfa_hip), Csize_t,
+                (Cint, Int64, Int64, Int64, Int64, Int64), fa_dtype(T), N, Nk, d, dv, B)
+    GC.@preserve q_lens k_lens with_workspace(nws) do ws
+        fa_check(ccall((:fa_varlen_bwd, libfa_hip), Cint,
+                       (Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float32},
+                        Ptr{Float32}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+                        Int64, Int64, Int64, Int64, Int64, Ptr{Cint}, Ptr{Cint}, Int64, Int64, Cfloat,
+                        Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+                       fa_dtype(T), Q, K, V, O, dO, l, m, dQ, dK, dV, N, Nk, d, dv, B,
+                       lens_ptr(q_lens, B), lens_ptr(k_lens, B), Int64(left), Int64(right), 0f0, ws, nws, stream_ptr()))
+    end
+    return dQ, dK, dV
+end
+
 # windowed_fa(q, k, v, ws; stride, pad) — src/windowed.jl:3-23 (fused on the device)
 function windowed_fa(q::ROCArray{T,N}, k::ROCArray{T,N}, v::ROCArray{T,N}, windowsize;
                      stride=windowsize, pad=(windowsize - 1) ÷ 2) where {T,N}

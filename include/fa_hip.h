@@ -362,6 +362,65 @@ int fa_local_bwd(int dtype,
                  float scale, void* workspace, size_t workspace_bytes,
                  void* hip_stream);
 
+/* Varlen attention: fa_local_fwd with per-slab lengths in a padded batch (documents of
+ * unequal length; decode requests with unequal KV caches).  q_lens and k_lens are DEVICE
+ * pointers to `batch` int32 values (`int` is int32_t on every ABI this library builds for; the
+ * library asserts it); NULL means "every slab is full on that side".  For slab b:
+ *   nq = clamp(q_lens[b], 0, N),  nk = clamp(k_lens[b], 0, Nk),  off_b = nk - nq  (either sign);
+ * the slab is the leading nq rows of Q (and O, l, m) and the leading nk rows of K, V: the layout
+ * and strides are the (N, Nk) slab's.  Query i < nq attends the keys j with
+ *   0 <= j < nk   and   i + off_b - left <= j <= i + off_b + right,
+ * a negative or >= Nk side unbounded as for fa_local_fwd: (-1, -1) with lengths is a
+ * key-padding mask, (-1, 0) causal per sequence, bottom-right aligned (the KV-cache form).
+ * Fully written, exact zeros: rows i >= nq get O = 0, l = 0, m = -Inf (the Nk == 0 state of
+ * fa_dense_fwd); so does a query i < nq that sees no key (nk < nq under a right bound, or
+ * nk == 0).  The mask is a select: padding rows of Q, K, V may hold anything finite (the
+ * assumption fa_causal_fwd makes for a masked V) and change no bit of any output.
+ * The lengths are device data and no call synchronises, so they are not validated on the
+ * host: the kernels clamp them as above, which keeps every access inside the slab.
+ * Shape-level checks, their order and the empty cases are fa_local_fwd's (Nk < N is
+ * FA_ERR_UNSUPPORTED, N == 0 or batch == 0 a no-op that dereferences nothing), all before any
+ * launch.  A varlen call always runs the varlen instantiations of the kernels (the local
+ * bodies with per-slab extents), also with NULL lengths: the key loop is cut per workgroup
+ * and per wave by the lengths as well as by the window, so padding is skipped, not merely
+ * masked; never split-KV, never the one-wave-per-SIMD kernel. */
+int fa_varlen_fwd(int dtype,
+                  const void* Q, const void* K, const void* V,
+                  void* O, float* l, float* m,
+                  int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch,
+                  const int* q_lens, const int* k_lens,
+                  int64_t left, int64_t right,
+                  float scale, void* workspace, size_t workspace_bytes,
+                  void* hip_stream);
+
+/* Workspace bytes fa_varlen_fwd needs (0 is a valid answer): fa_local_fwd_workspace's answer
+ * for the shape.  It depends on the shape alone, not on the lengths, the window or the device. */
+size_t fa_varlen_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d,
+                               int64_t dv, int64_t batch);
+
+/* Workspace bytes fa_varlen_bwd needs: fa_local_bwd_workspace's answer for the shape. */
+size_t fa_varlen_bwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d,
+                               int64_t dv, int64_t batch);
+
+/* Varlen backward: the chain rule of fa_varlen_fwd over the visible keys, for the same lengths
+ * and window.  O, l, m are fa_varlen_fwd's outputs (FA_DTYPE_F64 recomputes the statistics in
+ * double).  Always the two-pass form, header plan 0 (fa_dense_bwd_handoff_status answers -1);
+ * dQ, dK, dV are fully written and all three are bitwise reproducible.  Exact zeros: dQ rows
+ * i >= nq and the rows of queries that see no key; dK, dV rows j >= nk and the rows of keys
+ * that no query sees.  An empty row is chosen from the lengths and the window, never from the
+ * caller's l, and contributes nothing to any gradient.  Padding rows of Q, K, V and dO may hold
+ * anything finite.  Checks and empty inputs as fa_varlen_fwd. */
+int fa_varlen_bwd(int dtype,
+                  const void* Q, const void* K, const void* V,
+                  const void* O, const void* dO,
+                  const float* l, const float* m,
+                  void* dQ, void* dK, void* dV,
+                  int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch,
+                  const int* q_lens, const int* k_lens,
+                  int64_t left, int64_t right,
+                  float scale, void* workspace, size_t workspace_bytes,
+                  void* hip_stream);
+
 /* Standalone fused softmax, replaces
  *   fused_softmax!(P, S; dims)   reference src/fused_softmax.jl:1-41
  * (device versions src/cuda/fused_softmax.jl:11-314).  S, P: (M, N, batch)
