@@ -122,6 +122,21 @@ int fa_debug_set_fwd_variant(int v) {
 // one-wave-per-SIMD kernel (fa_fwd_p4.hip), 0 otherwise (tests, bench labels).
 int fa_debug_fwd_last_path(void) { return fa::g_fwd_last_path; }
 
+// Not part of the public header (tests): what the calling thread's last dense-family forward
+// and backward (dense, causal, local, varlen) launched, as recorded by the launchers after a
+// successful launch: out[0..2] the forward's fa::DenseFwdKernel, fa::DenseMask and pad flag (K / V
+// ran from the zero-padded copies), out[3..5] the backward's fa::DenseBwdKernel, fa::DenseMask
+// and padded flag (the kernels ran on the padded slabs).  -1 in all three of a direction that
+// has not launched on this thread.  Returns 0 (-1: out is null).
+int fa_debug_dense_last_launch(int* out) {
+    if (!out) return -1;
+    for (int i = 0; i < 3; ++i) {
+        out[i] = fa::g_dense_fwd_last[i];
+        out[3 + i] = fa::g_dense_bwd_last[i];
+    }
+    return 0;
+}
+
 // Not part of the public header: lazy-rescale threshold of the bf16/f16 forward
 // kernels in log2 units (default 8; 0 = rescale on every max increase, the
 // textbook order).  Accuracy tests only; returns the previous value.

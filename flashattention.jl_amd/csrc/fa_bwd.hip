@@ -1932,6 +1932,8 @@ static hipError_t launch_typed(const DenseBwdPlan& pl, const BwdParams& p, Dense
     return launch_generic<T>(p, mask, s);
 }
 
+thread_local int g_dense_bwd_last[3] = {-1, -1, -1};   // fa_debug_dense_last_launch: kernel, mask, padded
+
 static DenseBwdKnobs bwd_knobs() { return {g_bwd_force_generic, g_bwd_mode, g_bwd_hoff, g_bwd_xcd}; }
 
 // The shape's own needs under the thread's knobs on the current device: aligned tensors, room
@@ -2051,6 +2053,7 @@ int launch_dense_bwd(const DenseBwdArgs& a, hipStream_t s, const char** why) {
             *why = hipGetErrorString(e);
             return FA_ERR_HIP;
         }
+        g_dense_bwd_last[0] = pl.kernel, g_dense_bwd_last[1] = a.mask, g_dense_bwd_last[2] = pl.padded;
         return FA_OK;
     }
     if (pl.padded && !pl.slabs_fit) {
@@ -2103,6 +2106,7 @@ int launch_dense_bwd(const DenseBwdArgs& a, hipStream_t s, const char** why) {
         *why = hipGetErrorString(e);
         return FA_ERR_HIP;
     }
+    g_dense_bwd_last[0] = pl.kernel, g_dense_bwd_last[1] = a.mask, g_dense_bwd_last[2] = pl.padded;
     return FA_OK;
 }
 

@@ -67,6 +67,7 @@ namespace fa {
 
 thread_local int g_fwd_variant = kFwdAuto;   // a DenseFwdVariant (fa_dense_plan.h): benchmark knob, fa_debug_set_fwd_variant
 thread_local int g_fwd_last_path = 0;   // fa_debug_fwd_last_path: 30 when the last fast launch ran fa_fwd_p4
+thread_local int g_dense_fwd_last[3] = {-1, -1, -1};   // fa_debug_dense_last_launch: kernel, mask, pad
 thread_local float g_fwd_rescale_log2 = kRescaleLog2;  // fa_debug_set_rescale_threshold (accuracy tests)
 thread_local int g_causal_rev = 2;   // causal fast forward: launch order of the query blocks (fa_debug_set_causal_order)
 
@@ -1382,7 +1383,11 @@ size_t dense_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t 
 
 int launch_dense_fwd(const DenseArgs& a, hipStream_t s, const char** why) {
     g_fwd_last_path = 0;   // every path below that is not a persistent kernel leaves 0
-    if (a.dtype == FA_DTYPE_F64) return launch_dense_fwd_f64(a, s, why);   // kDenseFwdF64: it makes its own checks
+    if (a.dtype == FA_DTYPE_F64) {   // kDenseFwdF64: it makes its own checks
+        const int rc = launch_dense_fwd_f64(a, s, why);
+        if (rc == FA_OK) g_dense_fwd_last[0] = kDenseFwdF64, g_dense_fwd_last[1] = a.mask, g_dense_fwd_last[2] = 0;
+        return rc;
+    }
     const int Dc = head_dim_class(a.d), DVc = head_dim_class(a.dv);
     if (!Dc || !DVc) {
         *why = "head dimension exceeds the compiled maximum (128)";
@@ -1462,6 +1467,7 @@ int launch_dense_fwd(const DenseArgs& a, hipStream_t s, const char** why) {
         *why = hipGetErrorString(e);
         return FA_ERR_HIP;
     }
+    g_dense_fwd_last[0] = pl.kernel, g_dense_fwd_last[1] = pl.mask, g_dense_fwd_last[2] = pl.pad;
     return FA_OK;
 }
 

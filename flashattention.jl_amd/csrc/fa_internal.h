@@ -286,6 +286,9 @@ inline bool by_mask(DenseMask mask, F&& f) {
 // on the default paths and the public entry points remain stateless for them.
 extern thread_local int g_fwd_variant;        // forward kernel variant (a DenseFwdVariant, fa_dense_plan.h)
 extern thread_local int g_fwd_last_path;      // 30 when the last fast forward launch ran fa_fwd_p4
+// fa_debug_dense_last_launch: what the last dense-family forward / backward of this thread launched:
+// {a DenseFwdKernel / DenseBwdKernel, the DenseMask, pad / padded}; {-1, -1, -1} before the first
+extern thread_local int g_dense_fwd_last[3], g_dense_bwd_last[3];
 extern thread_local float g_fwd_rescale_log2; // forward fast kernels: lazy-rescale threshold (log2 units)
 extern thread_local int g_causal_rev;         // causal fast forward: launch order of the query blocks (0, 1, 2: fa_debug_set_causal_order)
 extern thread_local int g_bwd_force_generic;  // backward: force the generic SIMT path

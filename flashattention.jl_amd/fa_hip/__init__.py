@@ -200,6 +200,9 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, dbg):
             getattr(L, dbg).restype = ctypes.c_int
             getattr(L, dbg).argtypes = [ctypes.c_int]
+    if hasattr(L, "fa_debug_dense_last_launch"):
+        L.fa_debug_dense_last_launch.restype = ctypes.c_int
+        L.fa_debug_dense_last_launch.argtypes = [ctypes.POINTER(ctypes.c_int)]
     if hasattr(L, "fa_debug_set_rescale_threshold"):
         L.fa_debug_set_rescale_threshold.restype = ctypes.c_float
         L.fa_debug_set_rescale_threshold.argtypes = [ctypes.c_float]

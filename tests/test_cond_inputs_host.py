@@ -196,6 +196,28 @@ def test_hot_pairs_follow_the_mask():
             assert mk[i, j]
 
 
+def test_hot_pairs_are_unchanged_where_every_key_is_seen():
+    """hot_pairs takes its keys from the thirds of the SEEN keys.  Where every key is seen (no
+    mask, a causal mask, a circulant band) that is the thirds of [0, Nk): the values below are the
+    ones the helper returned before it learned of unseen keys, and the hotkeys inputs built on them
+    are the same bits (CRC-32 of k's bytes)."""
+    import zlib
+    assert C.hot_pairs(256, 256, 2) == [(51, 42, 0), (161, 129, 1), (8, 215, 0)]
+    assert C.hot_pairs(30, 2, 3) == [(13, 0, 0), (3, 1, 1)]
+    assert C.hot_pairs(200, 328, 2, C.causal_mask(200, 328)) == [(100, 54, 0), (118, 165, 1), (173, 275, 0)]
+    assert C.hot_pairs(520, 584, 2, C.causal_mask(520, 584)) == [(276, 97, 0), (374, 293, 1), (472, 488, 0)]
+    assert C.hot_pairs(77, 130, 1, C.causal_mask(77, 130)) == [(38, 21, 0), (45, 66, 0), (67, 110, 0)]
+    assert C.hot_pairs(136, 136, 1, C.band_mask(136, 33)) == [(22, 22, 0), (69, 69, 0), (115, 115, 0)]
+    assert C.hot_pairs(64, 64, 2, C.band_counts(64, 150) > 0) == [(32, 10, 0), (32, 33, 1), (32, 55, 0)]
+    q, k, _, _, _ = C.family("hotkeys", 200, 328, 128, 64, 2, "bfloat16", mask=C.causal_mask(200, 328))
+    assert (zlib.crc32(k.tobytes()), zlib.crc32(q.tobytes())) == (3780295603, 2238232506)
+    q, k, _, _, _ = C.family("hotkeys", 256, 256, 64, 64, 2, "float16")
+    assert (zlib.crc32(k.tobytes()), zlib.crc32(q.tobytes())) == (2961104623, 436521518)
+    # a per-slab mask that is the same in every slab is the shared mask
+    mk = C.causal_mask(200, 328)
+    assert C.hot_pairs(200, 328, 2, np.repeat(mk[:, :, None], 2, axis=2)) == C.hot_pairs(200, 328, 2, mk)
+
+
 @pytest.mark.parametrize("s", [0.05, 0.7])
 def test_oracle_scale_is_a_rescaling_of_q_and_k(s):
     rng = np.random.default_rng(7)
