@@ -1,7 +1,8 @@
-// fa_bwd_common.h — device pieces shared by the dense backward (fa_bwd.hip) and the
+// fa_bwd_common.h — device pieces shared by the dense backward (fa_bwd*.hip) and the
 // circulant backward (fa_circulant_bwd.hip): the swizzled 64-token LDS image of their
 // MFMA kernels (the one statement of its layout: the writers' chunk map and the
-// readers) and the vectorised pre-pass body.
+// readers) and the vectorised pre-pass body; then what the dense MFMA kernel files
+// share among themselves.
 #pragma once
 
 #include "fa_common.h"
@@ -58,7 +59,7 @@ __device__ __forceinline__ typename Frag8<T>::type img_row(const char* img, int 
 }
 
 // A lane's reader, built once per kernel from the thread's index in its workgroup.
-// (bwd_fused, fa_bwd.hip, is the one kernel that writes these offsets out itself and
+// (bwd_fused, fa_bwd_fused.hip, is the one kernel that writes these offsets out itself and
 // calls img_tr / img_row: see there.  A change to tro is made in both places.)
 template <class T>
 struct ImgReader {
@@ -131,5 +132,43 @@ __device__ __forceinline__ void prepass_rows8(const T* O, const T* dO, const flo
         nlse[idx + k] = -(m[idx + k] + logf(l[idx + k])) / scale;
     }
 }
+
+// --------------------------------------------------------------------------
+// Dense MFMA backward (fa_bwd_dq.hip, fa_bwd_dkdv.hip, fa_bwd_fused.hip): a slab's buffer
+// descriptor, the LDS-DMA of one image by 4 waves, the single pass's inter-workgroup words
+// and its dQᵀ column order.
+// --------------------------------------------------------------------------
+template <class T>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t bslab(const void* base, int64_t off_elems, int64_t elems) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)((const T*)base + off_elems), (short)0,
+                                             (int)(elems * (int64_t)sizeof(T)), 0x00020000);
+}
+
+// LDS-DMA one [R rows][64 tokens] image (R*128 bytes) from a [*][ntok] slab at
+// token t0.  4 waves; each wave-instruction fills 1 KiB (8 rows) lane-linearly,
+// so the swizzle is applied to the per-lane GLOBAL address (cdna guide rule 21).
+template <int R>
+__device__ __forceinline__ void dma_image(__amdgpu_buffer_rsrc_t rs, char* img, int ntok, int t0, int wave, int lane) {
+#pragma unroll
+    for (int it = 0; it < R / 32; ++it) {
+        const int blk = it * 4 + wave;                    // 1-KiB block of the image
+        const ImgChunk ch = img_chunk(blk * 64 + lane);   // row and chunk of the 16 B this lane fills
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(
+            rs, (__attribute__((address_space(3))) void*)(img + blk * 1024), 16,
+            (ch.f * ntok + t0 + 8 * ch.c) * 2, 0, 0, 0);
+    }
+}
+
+// Inter-workgroup words of the single-pass kernel: global (never flat), agent
+// scope, relaxed (global_load / global_store ... sc1).
+typedef __attribute__((address_space(1))) unsigned gu32;
+__device__ __forceinline__ unsigned ld_agent(gu32* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void st_agent(gu32* p, unsigned v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ int sig32(int r) { return (r & ~12) | ((r & 4) << 1) | ((r & 8) >> 1); }
 
 }  // namespace fa

@@ -791,7 +791,7 @@ def backward_handoff_trips(device=None) -> int:
     return _backward_header_word(2, device)
 
 
-_BWD_HDR_MAGIC = 0x46414200   # kBwdHdrMagic (fa_bwd.hip): "FAB\0" | plan in the low byte
+_BWD_HDR_MAGIC = 0x46414200   # kBwdHdrMagic (fa_bwd_params.h): "FAB\0" | plan in the low byte
 _HDR_PTR = {}                  # (device, stream) -> data_ptr of the scratch buffer at the first header read
 
 

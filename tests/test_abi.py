@@ -34,13 +34,13 @@ def test_header_declares_the_boundary():
 
 def test_header_states_the_kernels_give_up_bound():
     """The boundary contract's hand-off give-up bound is the one bwd_fused implements:
-    fa_bwd.hip takes kStallUs from the header's macro, and the prose around it states
+    fa_bwd_params.h takes kStallUs from the header's macro, and the prose around it states
     the same figure (in ms) and the no-progress rule (INTEGRATION.md agrees)."""
     hdr = open(HEADER).read()
     m = re.search(r"#define\s+FA_BWD_HANDOFF_STALL_US\s+(\d+)", hdr)
     assert m, "FA_BWD_HANDOFF_STALL_US missing from fa_hip.h"
     us = int(m.group(1))
-    src = open(os.path.join(ROOT, "flashattention.jl_amd", "csrc", "fa_bwd.hip")).read()
+    src = open(os.path.join(ROOT, "flashattention.jl_amd", "csrc", "fa_bwd_params.h")).read()
     k = re.search(r"constexpr\s+int\s+kStallUs\s*=\s*(\w+)\s*;", src)
     assert k and k.group(1) in ("FA_BWD_HANDOFF_STALL_US", str(us)), "kStallUs does not follow the header"
     prose = re.sub(r"\s+", " ", hdr)

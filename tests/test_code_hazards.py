@@ -1,7 +1,7 @@
 """The built gfx950 code object has no VALU-writes-SGPR -> vector-memory-reads-SGPR
 hazard closer than the 5 wait states the ISA requires (tools/vmem_sgpr_hazards.py).
 The compiler's hazard recognizer inserts those wait states for the instructions it
-emits, not in front of inline asm: fa_bwd.hip's asm LDS-DMA loads carry an `s_nop 4`
+emits, not in front of inline asm: fa_bwd_fused.hip's asm LDS-DMA loads carry an `s_nop 4`
 (a spilled descriptor restored by v_readlane right before one gave wrong dQ/dK/dV at
 d = 32), and its asm running-sum loads carry none, which this test keeps honest for
 whatever the compiler's register allocation does.  CPU only: it reads the library."""

@@ -338,7 +338,7 @@ def test_backward_two_streams_concurrent(fa):
     """Two configs[3]-sized backward calls (N 8192, d 128, 64 slabs) on two streams at
     once, each holding CUs the other's single pass would use.  Every hand-off wait of
     the single pass is on a member of lower launch id (two chains per slice, cut where
-    the rotated order wraps: fa_bwd.hip bwd_fused), so neither call can strand: both
+    the rotated order wraps: fa_bwd_fused.hip bwd_fused), so neither call can strand: both
     must complete their hand-off (status 0 on every concurrent call, no slab given up
     and recomputed) and match the float64 oracle on one slab each.  Timing is reported,
     and bounded only loosely (2.5x the same pair back to back on one stream, against

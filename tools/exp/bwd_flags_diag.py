@@ -1,5 +1,5 @@
 """After one solo single-pass backward, read the hand-off words of the workspace
-(FusedFlags in fa_bwd.hip): how many wrapped slices needed bwd_dq_fast's combine
+(FusedFlags in fa_dense_plan.h): how many wrapped slices needed bwd_dq_fast's combine
 (fin == 2), the comb word, trips, and the members' XCD words.  Debugging aid."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -14,7 +14,7 @@ CS = os.path.join(ROOT, "flashattention.jl_amd", "csrc")
 so = lambda abl: os.path.join(HERE, f"libfwd_stamp{abl}.so")
 abls = [int(a) for a in sys.argv[2:]] or [0]
 if sys.argv[1] == "build":
-    objs = [os.path.join(CS, "build", f + ".o") for f in ("fa_bwd.hip", "fa_windowed_fwd.hip", "fa_windowed_bwd.hip", "fa_circulant.hip",
+    objs = [os.path.join(CS, "build", f + ".o") for f in ("fa_bwd.hip", "fa_bwd_simt_dq.hip", "fa_bwd_simt_dkdv.hip", "fa_bwd_f32.hip", "fa_bwd_dq.hip", "fa_bwd_dkdv.hip", "fa_bwd_fused.hip", "fa_windowed_fwd.hip", "fa_windowed_bwd.hip", "fa_circulant.hip",
                                                           "fa_softmax.hip", "fa_f64.hip")]
     for abl in abls:
         subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-shared",

@@ -11,7 +11,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "build":
     for a in MODES:
         subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-shared",
                         "-fno-gpu-rdc", f"-DFA_WIN_ABL={a}", "-o", so(a), "-x", "hip", os.path.join(HERE, "win_ablate.hip"),
-                        "-x", "none", os.path.join(B, "fa_fwd.hip.o"), os.path.join(B, "fa_bwd.hip.o")], check=True)
+                        "-x", "none", os.path.join(B, "fa_fwd.hip.o"), *(os.path.join(B, f + ".hip.o") for f in ("fa_bwd", "fa_bwd_simt_dq", "fa_bwd_simt_dkdv", "fa_bwd_f32", "fa_bwd_dq", "fa_bwd_dkdv", "fa_bwd_fused"))], check=True)
     sys.exit(0)
 sys.path[:0] = [ROOT, os.path.join(ROOT, "flashattention.jl_amd")]
 import numpy as np, torch, fa_hip

@@ -3,7 +3,7 @@ hazard recognizer does not see through inline asm: a VALU instruction that write
 SGPR (v_readlane_b32 restoring a spilled SGPR, v_readfirstlane_b32, a VOP3 compare
 or carry-out) followed, within 5 wait states, by a vector-memory instruction that
 reads that SGPR as its buffer descriptor or scalar base/offset.  The ISA requires 5
-wait states between the two; the asm buffer loads of fa_bwd.hip carry an `s_nop 4`
+wait states between the two; the asm buffer loads of fa_bwd_fused.hip carry an `s_nop 4`
 only where a spill restore can land in front of them (the LDS-DMA descriptors), so
 this check guards the others.
 
