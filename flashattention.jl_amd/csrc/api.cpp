@@ -15,6 +15,7 @@
 
 #include "../../include/fa_hip.h"
 #include "fa_circulant_plan.h"   // the circulant plans (host functions)
+#include "fa_decode_plan.h"   // the decode plan (host functions)
 #include "fa_dense_plan.h"   // the dense plans (host functions)
 #include "fa_internal.h"
 #include "fa_windowed.h"   // the windowed plans (host functions; no kernel is instantiated here)
@@ -642,6 +643,67 @@ int fa_varlen_bwd(int dtype, const void* Q, const void* K, const void* V, const 
                   void* hip_stream) {
     return dense_family_bwd(fa::kMaskVarlen, "fa_varlen_bwd", dtype, Q, K, V, O, dO, l, m, dQ, dK, dV, N, Nk, d, dv, batch,
                             left, right, scale, workspace, workspace_bytes, hip_stream, q_lens, k_lens);
+}
+
+// ---------------------------------------------------------------------------------------
+// Decode attention (fa_decode.hip): fa_varlen_fwd's forward with `group` query slabs per KV
+// slab, split over the keys.  Checks in fa_varlen_fwd's order and words, all before any launch.
+// ---------------------------------------------------------------------------------------
+
+// Not part of the public header: the number of key ranges a decode call is cut into (0: the
+// plan's own choice; n > 0 forces n, clamped to the shape's tile count).  Thread-local; returns
+// the previous value.  fa_decode_fwd_workspace answers for the value in force.
+int fa_debug_set_decode_nsplit(int n) {
+    const int old = fa::g_decode_nsplit;
+    if (n >= 0) fa::g_decode_nsplit = n;
+    return old;
+}
+// Not part of the public header (tests): fa::decode_plan for the shape, a forced range count
+// and the K / V alignment fact.  Returns the kernel, a fa::DecodeKernel (-1: refused), and
+// writes out[4] = {kernel, nsplit, grid, workspace bytes} (out may be null).
+int fa_debug_decode_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, int64_t group,
+                         int force_nsplit, int kv_aligned16, int64_t* out) {
+    const fa::DecodePlan pl = fa::decode_plan(dtype, N, Nk, d, dv, batch, group, force_nsplit, kv_aligned16 != 0);
+    if (out) {
+        out[0] = pl.kernel; out[1] = pl.nsplit; out[2] = pl.grid; out[3] = (int64_t)pl.total;
+    }
+    return pl.kernel;
+}
+
+size_t fa_decode_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, int64_t group) {
+    return fa::decode_plan(dtype, N, Nk, d, dv, batch, group, fa::g_decode_nsplit, true).total;
+}
+
+int fa_decode_fwd(int dtype, const void* Q, const void* K, const void* V, void* O, float* l, float* m,
+                  int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, int64_t group,
+                  const int32_t* q_lens, const int32_t* k_lens, int64_t left, int64_t right, float scale,
+                  void* workspace, size_t workspace_bytes, void* hip_stream) {
+    const char* const fn = "fa_decode_fwd";
+    if (!valid_dtype(dtype)) return fail(FA_ERR_INVALID_ARG, fn, "unknown dtype");
+    if (N == 0 || batch == 0) return ok();   // no query: nothing to write, nothing dereferenced
+    if (!Q || !K || !V || !O || !l || !m) return fail(FA_ERR_INVALID_ARG, fn, "null pointer");
+    if (N < 0 || Nk < 0 || d < 1 || dv < 1 || batch < 0 || group < 1)
+        return fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: N, Nk, batch must be >= 0, d, dv >= 1 and group >= 1");
+    if (d > fa::kMaxHeadDim || dv > fa::kMaxHeadDim)
+        return fail(FA_ERR_UNSUPPORTED, fn, "head dimension exceeds the compiled maximum (128)");
+    if (Nk < N) return fail(FA_ERR_UNSUPPORTED, fn, "decode attention needs Nk >= N (a query would see no key)");
+    if (N * group > fa::kDecodeRows)
+        return fail(FA_ERR_UNSUPPORTED, fn, "decode attention takes N * group <= 32 query rows per KV slab; use fa_varlen_fwd");
+    if (!fa::dense_16bit(dtype))
+        return fail(FA_ERR_UNSUPPORTED, fn, "decode attention is bf16 / fp16 only; use fa_varlen_fwd");
+    // a slab, and one key tile past it, within the descriptors' 32-bit byte offsets
+    if (Nk > INT32_MAX / 2 || (Nk + fa::kDecodeKeyTile) * (d > dv ? d : dv) * 2 >= (int64_t)INT32_MAX ||
+        batch * group > INT32_MAX / 64)
+        return fail(FA_ERR_UNSUPPORTED, fn, "extent exceeds the kernels' 32-bit addressing");
+    const fa::DecodePlan pl = fa::decode_plan(dtype, N, Nk, d, dv, batch, group, fa::g_decode_nsplit,
+                                              fa::aligned16(K) && fa::aligned16(V));
+    if (pl.total > 0 && (!workspace || workspace_bytes < pl.total))
+        return fail(FA_ERR_WORKSPACE, fn, "workspace missing or smaller than fa_decode_fwd_workspace()");
+    fa::DecodeArgs a{dtype, Q, K, V, O, l, m, N, Nk, d, dv, batch, group, q_lens, k_lens, left, right,
+                     resolve_scale(scale, d), workspace, workspace_bytes};
+    const char* why = "";
+    const int rc = fa::launch_decode_fwd(a, (hipStream_t)hip_stream, &why);
+    return rc == FA_OK ? ok() : fail(rc, fn, why);
 }
 
 // Not part of the public header: launch order of the causal fast forward's query blocks

@@ -1,0 +1,81 @@
+// fa_decode_plan.h — the HOST PLAN of decode attention (fa_decode.hip): how many key ranges
+// a call is split into, which instantiation runs, on what grid, and how large the workspace of
+// partials is.  decode_plan is a pure function of the shape, the forced range count
+// (fa_debug_set_decode_nsplit) and the K / V alignment fact: no device query, no thread-local
+// read, nothing from the lengths or the window (they are device data; the kernel cuts each
+// slab's own visible range into the plan's nsplit shares).  The launcher asks once, the
+// workspace entry point returns the same plan's total, fa_debug_decode_plan (api.cpp) returns
+// it for tests/test_decode_host.py.
+#pragma once
+
+#include <algorithm>
+
+#include "fa_dense_plan.h"
+
+namespace fa {
+
+struct DecodeArgs {
+    int dtype;                 // FA_DTYPE_BF16 or FA_DTYPE_F16
+    const void *Q, *K, *V;
+    void* O;
+    float *l, *m;
+    int64_t N, Nk, d, dv, batch, group;   // batch: KV slabs; Q, O, l, m have batch * group slabs
+    const int32_t *q_lens, *k_lens;       // device, `batch` values each, or nullptr (full)
+    int64_t left, right;
+    float scale;               // already resolved (> 0)
+    void* workspace;
+    size_t workspace_bytes;
+};
+
+constexpr int kDecodeRows = 32;       // rows of the one MFMA row tile: N * group <= 32
+constexpr int kDecodeKeyTile = 64;    // keys per tile
+constexpr int kDecodeThreads = 256;   // 4 waves, each on alternate key tiles of the workgroup's range
+
+enum DecodeKernel : int {
+    kDecodeNone = -1,     // refused (dtype, head dims, rows)
+    kDecodeVec = 0,       // decode_fwd<.., VEC = true>: 16-B K DMA into LDS, 16-B V loads
+    kDecodeNarrow = 1,    // decode_fwd<.., VEC = false>: 2-byte loads (Nk % 8 != 0 or misaligned K / V); no copies
+};
+
+struct DecodePlan {
+    DecodeKernel kernel = kDecodeNone;
+    int nsplit = 1;          // key ranges per KV slab (1: the workgroup stores O, l, m itself)
+    int64_t grid = 0;        // workgroups of decode_fwd: batch * nsplit
+    int64_t combine_grid = 0;   // workgroups of decode_combine (0 when nsplit == 1)
+    size_t total = 0;        // workspace bytes: [nsplit][batch * group][N][dv + 2] floats + 256 (0 when nsplit == 1)
+};
+
+// Split by shape, as dense_fwd_split: fewer than kFwdSplitBelow slabs split the keys so that
+// about kFwdSplitTarget workgroups run, each range at least 2 key tiles.  force: 0 auto, n > 0
+// that many ranges, clamped to the shape's tile count.
+inline int decode_nsplit(int64_t Nk, int64_t batch, int force) {
+    const int64_t NT = ceil_div(Nk, kDecodeKeyTile);
+    if (force > 0) return (int)std::max<int64_t>(1, std::min<int64_t>(force, NT));
+    if (batch >= kFwdSplitBelow || NT < 4) return 1;
+    int64_t ns = std::min<int64_t>(ceil_div(kFwdSplitTarget, batch), NT / 2);
+    if (ns < 2) return 1;
+    ns = ceil_div(NT, ceil_div(NT, ns));
+    return ns < 2 ? 1 : (int)ns;
+}
+
+inline DecodePlan decode_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, int64_t group,
+                              int force_nsplit, bool kv_aligned16) {
+    DecodePlan pl;
+    if (!dense_16bit(dtype) || !head_dim_class(d) || !head_dim_class(dv) || N < 1 || group < 1 ||
+        N * group > kDecodeRows || Nk < N || batch < 1)
+        return pl;
+    pl.kernel = Nk % 8 == 0 && kv_aligned16 ? kDecodeVec : kDecodeNarrow;
+    pl.nsplit = decode_nsplit(Nk, batch, force_nsplit);
+    pl.grid = batch * pl.nsplit;
+    if (pl.nsplit > 1) {
+        pl.combine_grid = ceil_div(batch * group * N * dv, kDecodeThreads);
+        pl.total = (size_t)(pl.nsplit * batch * group * N * (dv + 2)) * sizeof(float) + 256;
+    }
+    return pl;
+}
+
+int launch_decode_fwd(const DecodeArgs& a, hipStream_t s, const char** why);
+
+extern thread_local int g_decode_nsplit;   // fa_debug_set_decode_nsplit: 0 auto, n forces n key ranges
+
+}  // namespace fa

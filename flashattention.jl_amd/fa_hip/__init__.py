@@ -44,6 +44,7 @@ __all__ = [
     "causal_fa", "causal_fa_", "causal_fa_backward", "causal_dpa",
     "local_fa", "local_fa_", "local_fa_backward", "local_dpa",
     "varlen_fa", "varlen_fa_", "varlen_fa_backward", "varlen_dpa",
+    "decode_fa", "decode_fa_",
     "fused_softmax", "fused_softmax_", "DTYPES",
 ]
 
@@ -190,6 +191,17 @@ def lib() -> ctypes.CDLL:
                                                ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(i64)]
         L.fa_debug_varlen_clamp.restype = ctypes.c_int
         L.fa_debug_varlen_clamp.argtypes = [ctypes.c_int, ctypes.c_int]
+    if hasattr(L, "fa_decode_fwd"):
+        L.fa_decode_fwd_workspace.restype = ctypes.c_size_t
+        L.fa_decode_fwd_workspace.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64, i64]
+        L.fa_decode_fwd.restype = ctypes.c_int
+        L.fa_decode_fwd.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, vp, vp, i64, i64,
+                                    f32, vp, ctypes.c_size_t, vp]
+        L.fa_debug_set_decode_nsplit.restype = ctypes.c_int
+        L.fa_debug_set_decode_nsplit.argtypes = [ctypes.c_int]
+        L.fa_debug_decode_plan.restype = ctypes.c_int
+        L.fa_debug_decode_plan.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64, i64, ctypes.c_int, ctypes.c_int,
+                                           ctypes.POINTER(i64)]
     L.fa_softmax_workspace.restype = ctypes.c_size_t
     L.fa_softmax_workspace.argtypes = [i64, i64, i64, ctypes.c_int]
     L.fa_softmax.restype = ctypes.c_int
@@ -818,6 +830,57 @@ def _backward_header_word(i: int, device=None) -> int:
     if i == 3:
         _require((words[0] & 0xFF) == 1, "header word 3 is defined only after a single-pass backward")
     return words[i]
+
+
+# ----------------------------------------------------------------------------
+# decode: a few queries per KV slab against a long cache, `group` query slabs sharing each
+# K / V slab, split over the keys (fa_decode_fwd; forward only)
+# ----------------------------------------------------------------------------
+def decode_fa_(O: torch.Tensor, l: torch.Tensor, m: torch.Tensor,
+               Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor,
+               k_lens=None, q_lens=None, group: int = 1, left: int = -1, right: int = 0,
+               scale: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """:func:`varlen_fa_`'s forward with a ``group`` factor, in place.  K (Nk, d, B) and
+    V (Nk, dv, B) hold B KV slabs; Q (N, d, B*group), O (N, dv, B*group), l, m (N, 1, B*group):
+    query slab bq uses KV slab bq // group.  k_lens, q_lens: B lengths, one per KV slab, shared by
+    its ``group`` query slabs (None: full).  The mask, l, m, O and the empty-row rule are
+    varlen_fa_'s; the defaults (-1, 0) are causal, bottom-right aligned.  N * group <= 32,
+    bf16 / fp16 only (FlashAttentionError otherwise: use varlen_fa_)."""
+    for t in (O, l, m, Q, K, V):
+        _require(t.dim() == 3, "decode_fa! expects 3-D (N, d, batch) arrays")
+    group = int(group)
+    _require(group >= 1, "DimensionMismatch: group must be >= 1")
+    N, d, BG = Q.shape
+    Nk, dv, B = K.shape[0], V.shape[1], K.shape[2]
+    _require(BG == B * group, f"Q has batch {BG}, expected {B} KV slabs x group {group} = {B * group}")
+    _require(K.shape == (Nk, d, B), f"K has shape {tuple(K.shape)}, expected ({Nk}, {d}, {B})")
+    _require(V.shape == (Nk, dv, B), f"V has shape {tuple(V.shape)}, expected ({Nk}, {dv}, {B})")
+    _require(O.shape == (N, dv, BG), f"O has shape {tuple(O.shape)}, expected ({N}, {dv}, {BG})")
+    _require(l.shape == (N, 1, BG) and m.shape == (N, 1, BG), "l, m must be (N, 1, batch * group)")
+    _require(l.dtype == torch.float32 and m.dtype == torch.float32, "l, m must be float32")
+    code = _dtype_code(Q, K, V, O)
+    _masked_extents("decode", N, Nk)
+    _device_check(Q, K, V, O, l, m)
+    ql = _lens(q_lens, N, B, Q.device, "q_lens")
+    kl = _lens(k_lens, Nk, B, Q.device, "k_lens")
+    Lb = lib()
+    nws = Lb.fa_decode_fwd_workspace(code, N, Nk, d, dv, B, group)
+    ws = _workspace(Q.device, nws) if nws else None
+    _check(Lb.fa_decode_fwd(code, _ptr(Q), _ptr(K), _ptr(V), _ptr(O), _ptr(l), _ptr(m), N, Nk, d, dv, B, group,
+                            _ptr(ql), _ptr(kl), int(left), int(right), float(scale), _ptr(ws), int(nws), _stream(Q)))
+    return O, l, m
+
+
+def decode_fa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k_lens=None, q_lens=None, group: int = 1,
+              left: int = -1, right: int = 0, scale: float = 0.0):
+    """``decode_fa(q, k, v, k_lens, q_lens, group, left, right) -> (O, l, m)``: :func:`decode_fa_`
+    on fresh outputs.  q (N, d, B*group), k (Nk, d, B), v (Nk, dv, B) with Nk >= N."""
+    _require(q.dim() == 3 and k.dim() == 3 and v.dim() == 3, "decode_fa expects 3-D (N, d, batch) arrays")
+    N, _, BG = q.shape
+    O = jl_empty((N, v.shape[1], BG), q.dtype, q.device)
+    l = jl_empty((N, 1, BG), torch.float32, q.device)
+    m = jl_empty((N, 1, BG), torch.float32, q.device)
+    return decode_fa_(O, l, m, q, k, v, k_lens, q_lens, group, left, right, scale)
 
 
 # ----------------------------------------------------------------------------

@@ -510,6 +510,43 @@ function varlen_fa(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3}; kw...) 
     return varlen_fa!(O, l, m, Q, K, V; kw...)
 end
 
+# decode_fa!(O, l, m, Q, K, V; k_lens, q_lens, group, left, right) — varlen_fa!'s forward with
+# `group` query slabs per KV slab, split over the keys (the reference has none; forward only).
+# K (Nk, d, B), V (Nk, dv, B); Q (N, d, B*group), O (N, dv, B*group), l, m (N, 1, B*group): query
+# slab bq uses KV slab div(bq, group) (0-based).  Lengths: one per KV slab.  N * group <= 32,
+# BFloat16 / Float16 only.  The defaults (-1, 0) are causal, bottom-right aligned.
+function decode_fa!(O::ROCArray{T,3}, l::ROCArray{Float32,3}, m::ROCArray{Float32,3},
+                    Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3};
+                    k_lens=nothing, q_lens=nothing, group::Integer=1, left::Integer=-1, right::Integer=0) where {T}
+    N, d, BG = size(Q)
+    Nk, dv, B = size(K, 1), size(V, 2), size(K, 3)
+    group >= 1 && BG == B * group || throw(DimensionMismatch("Q must hold group query slabs per KV slab"))
+    size(K) == (Nk, d, B) || throw(DimensionMismatch("K"))
+    size(V) == (Nk, dv, B) || throw(DimensionMismatch("V"))
+    size(O) == (N, dv, BG) || throw(DimensionMismatch("O"))
+    size(l) == (N, 1, BG) && size(m) == (N, 1, BG) || throw(DimensionMismatch("l, m must be (N, 1, batch * group)"))
+    nws = ccall((:fa_decode_fwd_workspace, libfa_hip), Csize_t,
+                (Cint, Int64, Int64, Int64, Int64, Int64, Int64), fa_dtype(T), N, Nk, d, dv, B, group)
+    GC.@preserve q_lens k_lens with_workspace(nws) do ws
+        fa_check(ccall((:fa_decode_fwd, libfa_hip), Cint,
+                       (Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32},
+                        Int64, Int64, Int64, Int64, Int64, Int64, Ptr{Cint}, Ptr{Cint}, Int64, Int64, Cfloat,
+                        Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+                       fa_dtype(T), Q, K, V, O, l, m, N, Nk, d, dv, B, Int64(group), lens_ptr(q_lens, B),
+                       lens_ptr(k_lens, B), Int64(left), Int64(right), 0f0, ws, nws, stream_ptr()))
+    end
+    return O, l, m
+end
+
+# decode_fa(Q, K, V; k_lens, q_lens, group, left, right) -> (O, l, m), Float32 statistics
+function decode_fa(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3}; kw...) where {T}
+    N, BG = size(Q, 1), size(Q, 3)
+    O = similar(Q, N, size(V, 2), BG)
+    l = similar(Q, Float32, N, 1, BG)
+    m = similar(Q, Float32, N, 1, BG)
+    return decode_fa!(O, l, m, Q, K, V; kw...)
+end
+
 # varlen_fa_backward(Q, K, V, O, dO, l, m; q_lens, k_lens, left, right) -> (dQ, dK, dV): the
 # two-pass form, bitwise reproducible; exact zeros past the lengths and on empty rows
 function varlen_fa_backward(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3},

@@ -421,6 +421,47 @@ int fa_varlen_bwd(int dtype,
                   float scale, void* workspace, size_t workspace_bytes,
                   void* hip_stream);
 
+/* Decode attention: fa_varlen_fwd's forward with a `group` factor, split over the keys (a few
+ * queries per KV slab against a long cache; several query heads sharing one K / V slab).
+ * Forward only.  `batch` counts KV slabs: K is (Nk, d, batch), V (Nk, dv, batch); Q is
+ * (N, d, batch * group), O (N, dv, batch * group), l and m (N, 1, batch * group) float32.
+ * Query slab bq uses KV slab bq / group (the heads of a group are adjacent: with heads fastest
+ * in the flattened batch, query head h reads KV head h / group).  q_lens and k_lens are DEVICE
+ * pointers to `batch` int32 values, one per KV slab, shared by its `group` query slabs; NULL
+ * means full; they are clamped on the device exactly as for fa_varlen_fwd and never read or
+ * validated on the host.  Mask, l, m, O and the empty-row rule are fa_varlen_fwd's: per KV
+ * slab nq, nk, off = nk - nq and the window as there; query i < nq sees key j iff 0 <= j < nk
+ * and i + off - left <= j <= i + off + right; rows i >= nq and queries that see no key get
+ * O = +0, l = 0, m = -Inf, by select; padding rows of Q, K, V may hold anything finite and
+ * change no output bit.
+ * Limits: N * group <= 32 (all rows of a KV slab are one 32-row MFMA tile; more is
+ * FA_ERR_UNSUPPORTED: use fa_varlen_fwd); FA_DTYPE_BF16 and FA_DTYPE_F16 only (F32, F64:
+ * FA_ERR_UNSUPPORTED); 1 <= d, dv <= fa_max_head_dim().
+ * Checks, in order, all before any launch: null pointers; DimensionMismatch (group < 1
+ * included); head dims, Nk >= N, N * group <= 32 and dtype (FA_ERR_UNSUPPORTED); the
+ * kernels' 32-bit extents (a K / V slab below 2^31 bytes); the workspace.  N == 0 or
+ * batch == 0 is a no-op that dereferences nothing.
+ * K and V are never copied: Nk % 8 != 0, or a K / V pointer that is not 16-B aligned, selects
+ * an instantiation with narrower loads (slower, correct, no workspace slabs).  Each KV slab's
+ * visible key range is cut into the plan's number of equal shares, one workgroup each; the
+ * partial results are merged in a fixed order (no atomics, no hand-off between workgroups), so
+ * all outputs are bitwise reproducible for given lengths, and m, a max, is bitwise the same
+ * for every number of shares. */
+int fa_decode_fwd(int dtype,
+                  const void* Q, const void* K, const void* V,
+                  void* O, float* l, float* m,
+                  int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, int64_t group,
+                  const int* q_lens, const int* k_lens,
+                  int64_t left, int64_t right,
+                  float scale, void* workspace, size_t workspace_bytes,
+                  void* hip_stream);
+
+/* Workspace bytes fa_decode_fwd needs (0 is a valid answer: the keys are not split): the
+ * fp32 partials of the key shares plus 256 B of slack.  It depends on the shape alone, not on
+ * the lengths, the window or the device. */
+size_t fa_decode_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv,
+                               int64_t batch, int64_t group);
+
 /* Standalone fused softmax, replaces
  *   fused_softmax!(P, S; dims)   reference src/fused_softmax.jl:1-41
  * (device versions src/cuda/fused_softmax.jl:11-314).  S, P: (M, N, batch)

@@ -1,0 +1,120 @@
+"""Decode attention against varlen attention on decode shapes: forward device time, one process,
+one run (tools/varlen_time.py's method).
+
+    python tools/decode_time.py [--window-s 0.05] [--windows 5]
+
+Per shape (bf16, d = dv = 128, the causal window (-1, 0), nq queries per slab, B KV slabs, G query
+heads per KV slab, a cache of Nk keys) and per draw of the cache lengths (all full; a fixed-seed
+uniform draw on [Nk/8, Nk]): warm-up, then `windows` rounds; a round times one event-timed window
+of back-to-back calls (as many as fill `window-s` seconds, at least 3) of fa_decode_fwd and of
+fa_varlen_fwd with the same mask, interleaved, so that clock and co-tenant drift hit both alike.
+Everything goes through the C ABI with preallocated outputs, lengths and workspaces.
+
+The baseline for G > 1 runs on a cache REPEATED G times (B * G slabs), the only way fa_varlen_fwd
+serves grouped heads; the repeat is made once, outside the timed region.
+
+Prints the median and the spread of each, their ratio, and the decode time as a multiple of the
+byte floor (sum_b nk_b) * (d + dv) * 2 B / 8 TB/s.  Asserts that decode_fa is faster than its
+baseline by more than the larger of the two spreads (max - min of the windows).
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes
+import os
+import random
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "flashattention.jl_amd")]
+import torch  # noqa: E402
+
+import fa_hip  # noqa: E402
+
+D = 128
+SHAPES = [(1, B, G, Nk) for B in (8, 128) for G in (1, 8) for Nk in (8192, 32768)] + [(4, 8, 8, 32768)]   # (nq, B, G, Nk)
+HBM_BYTES_PER_S = 8e12
+
+
+def window(fn, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) * 1e-3 / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--window-s", type=float, default=0.05)
+    ap.add_argument("--windows", type=int, default=5)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "needs a ROCm device"
+    L = fa_hip.lib()
+    g = torch.Generator(device="cuda").manual_seed(1)
+    P = lambda t: ctypes.c_void_p(t.data_ptr())
+    dt = torch.bfloat16
+    code = fa_hip.DTYPES[dt]
+    left, right = -1, 0
+    print(f"device: {torch.cuda.get_device_name(0)}; {a.windows} interleaved windows of {a.window_s} s; bf16, d = dv = {D}, "
+          f"window ({left}, {right}); the varlen baseline of G > 1 runs on a cache repeated G times outside the timed region",
+          flush=True)
+    missed = []
+    for (N, B, G, Nk) in SHAPES:
+        mk = lambda n, b: fa_hip.jl_tensor(torch.randn((n, D, b), generator=g, device="cuda"), dt)
+        Q, K, V = mk(N, B * G), mk(Nk, B), mk(Nk, B)
+        # (Nk, D, B) column-major is [B][D][Nk] in memory: repeating slab b G times in place
+        rep = lambda t: t if G == 1 else fa_hip.jl_tensor(t.repeat_interleave(G, dim=2), dt)
+        KR, VR = rep(K), rep(V)
+        O, O2 = fa_hip.jl_empty((N, D, B * G), dt), fa_hip.jl_empty((N, D, B * G), dt)
+        l, m = fa_hip.jl_empty((N, 1, B * G)), fa_hip.jl_empty((N, 1, B * G))
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        nwd = max(L.fa_decode_fwd_workspace(code, N, Nk, D, D, B, G), 1)
+        nwv = max(L.fa_varlen_fwd_workspace(code, N, Nk, D, D, B * G), 1)
+        wsd, wsv = torch.empty(nwd, dtype=torch.uint8, device="cuda"), torch.empty(nwv, dtype=torch.uint8, device="cuda")
+        rnd = random.Random(7)
+        draws = {"full": [Nk] * B, "uniform": [rnd.randint(Nk // 8, Nk) for _ in range(B)]}
+        for name, kl in draws.items():
+            KL = torch.tensor(kl, dtype=torch.int32, device="cuda")
+            KLR = KL.repeat_interleave(G)
+
+            def dec():
+                rc = L.fa_decode_fwd(code, P(Q), P(K), P(V), P(O), P(l), P(m), N, Nk, D, D, B, G, None, P(KL), left, right,
+                                     0.0, P(wsd), nwd, st)
+                assert rc == 0, L.fa_last_error()
+
+            def var():
+                rc = L.fa_varlen_fwd(code, P(Q), P(KR), P(VR), P(O2), P(l), P(m), N, Nk, D, D, B * G, None, P(KLR), left, right,
+                                     0.0, P(wsv), nwv, st)
+                assert rc == 0, L.fa_last_error()
+
+            runs = [("decode", dec), ("varlen", var)]
+            reps = {}
+            for nm, fn in runs:
+                for _ in range(2):
+                    fn()
+                torch.cuda.synchronize()
+                reps[nm] = max(3, min(20000, int(a.window_s / window(fn, 3)) + 1))
+            times = {nm: [] for nm, _ in runs}
+            for _ in range(a.windows):
+                for nm, fn in runs:
+                    times[nm].append(window(fn, reps[nm]))
+            med = {k: statistics.median(v) for k, v in times.items()}
+            spread = max(max(v) - min(v) for v in times.values())
+            floor = sum(kl) * 2 * D * 2 / HBM_BYTES_PER_S
+            ok = med["varlen"] - med["decode"] > spread
+            print(f"nq {N} B {B:3d} G {G} Nk {Nk:5d} {name:7s}: decode {med['decode']*1e6:9.1f} us "
+                  f"[{min(times['decode'])*1e6:.1f}, {max(times['decode'])*1e6:.1f}]  varlen {med['varlen']*1e6:10.1f} us "
+                  f"[{min(times['varlen'])*1e6:.1f}, {max(times['varlen'])*1e6:.1f}]  varlen / decode {med['varlen']/med['decode']:7.2f}  "
+                  f"decode / byte floor {med['decode']/floor:6.2f}  {'ok' if ok else 'MISSED'}", flush=True)
+            if not ok:
+                missed.append(f"nq {N} B {B} G {G} Nk {Nk} {name}")
+        del Q, K, V, KR, VR
+    assert not missed, f"decode_fa is not faster than its varlen_fa baseline by more than the spread: {missed}"
+
+
+if __name__ == "__main__":
+    main()
