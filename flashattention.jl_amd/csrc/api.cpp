@@ -706,6 +706,57 @@ int fa_decode_fwd(int dtype, const void* Q, const void* K, const void* V, void* 
     return rc == FA_OK ? ok() : fail(rc, fn, why);
 }
 
+// Decode attention over an fp8 (e4m3fn) cache (fa_decode_fp8.hip): fa_decode_fwd's checks in
+// its order and words; the scales are device data and are not looked at here.
+// fa_debug_set_decode_nsplit governs this entry point too.
+
+// Not part of the public header (tests): fa::decode_fp8_plan, as fa_debug_decode_plan.
+int fa_debug_decode_fp8_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, int64_t group,
+                             int force_nsplit, int kv_aligned16, int64_t* out) {
+    const fa::DecodePlan pl = fa::decode_fp8_plan(dtype, N, Nk, d, dv, batch, group, force_nsplit, kv_aligned16 != 0);
+    if (out) {
+        out[0] = pl.kernel; out[1] = pl.nsplit; out[2] = pl.grid; out[3] = (int64_t)pl.total;
+    }
+    return pl.kernel;
+}
+
+size_t fa_decode_fp8_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, int64_t group) {
+    return fa::decode_fp8_plan(dtype, N, Nk, d, dv, batch, group, fa::g_decode_nsplit, true).total;
+}
+
+int fa_decode_fp8_fwd(int dtype, const void* Q, const void* K8, const void* V8, const float* k_scale, const float* v_scale,
+                      void* O, float* l, float* m, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch,
+                      int64_t group, const int32_t* q_lens, const int32_t* k_lens, int64_t left, int64_t right, float scale,
+                      void* workspace, size_t workspace_bytes, void* hip_stream) {
+    const char* const fn = "fa_decode_fp8_fwd";
+    if (!valid_dtype(dtype)) return fail(FA_ERR_INVALID_ARG, fn, "unknown dtype");
+    if (N == 0 || batch == 0) return ok();   // no query: nothing to write, nothing dereferenced
+    if (!Q || !K8 || !V8 || !O || !l || !m) return fail(FA_ERR_INVALID_ARG, fn, "null pointer");
+    if (N < 0 || Nk < 0 || d < 1 || dv < 1 || batch < 0 || group < 1)
+        return fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: N, Nk, batch must be >= 0, d, dv >= 1 and group >= 1");
+    if (d > fa::kMaxHeadDim || dv > fa::kMaxHeadDim)
+        return fail(FA_ERR_UNSUPPORTED, fn, "head dimension exceeds the compiled maximum (128)");
+    if (Nk < N) return fail(FA_ERR_UNSUPPORTED, fn, "decode attention needs Nk >= N (a query would see no key)");
+    if (N * group > fa::kDecodeRows)
+        return fail(FA_ERR_UNSUPPORTED, fn, "decode attention takes N * group <= 32 query rows per KV slab; use fa_varlen_fwd");
+    if (!fa::dense_16bit(dtype))
+        return fail(FA_ERR_UNSUPPORTED, fn, "decode attention is bf16 / fp16 only (Q and O; the cache is e4m3fn)");
+    // a slab of bytes, and one key tile past it, within the descriptors' 32-bit byte offsets
+    if (Nk > INT32_MAX / 2 || (Nk + fa::kDecodeKeyTile) * (d > dv ? d : dv) >= (int64_t)INT32_MAX ||
+        batch * group > INT32_MAX / 64)
+        return fail(FA_ERR_UNSUPPORTED, fn, "extent exceeds the kernels' 32-bit addressing");
+    const fa::DecodePlan pl = fa::decode_fp8_plan(dtype, N, Nk, d, dv, batch, group, fa::g_decode_nsplit,
+                                                  fa::aligned16(K8) && fa::aligned16(V8));
+    if (pl.total > 0 && (!workspace || workspace_bytes < pl.total))
+        return fail(FA_ERR_WORKSPACE, fn, "workspace missing or smaller than fa_decode_fp8_fwd_workspace()");
+    fa::DecodeFp8Args a{{dtype, Q, K8, V8, O, l, m, N, Nk, d, dv, batch, group, q_lens, k_lens, left, right,
+                         resolve_scale(scale, d), workspace, workspace_bytes},
+                        k_scale, v_scale};
+    const char* why = "";
+    const int rc = fa::launch_decode_fp8_fwd(a, (hipStream_t)hip_stream, &why);
+    return rc == FA_OK ? ok() : fail(rc, fn, why);
+}
+
 // Not part of the public header: launch order of the causal fast forward's query blocks
 // 0 in order; 1 slab by slab, a slab's heaviest (last) block first; 2 block-major inside each
 // XCD's share of the grid, heaviest blocks of all its slabs first (where that share holds

@@ -5,7 +5,8 @@
 // read, nothing from the lengths or the window (they are device data; the kernel cuts each
 // slab's own visible range into the plan's nsplit shares).  The launcher asks once, the
 // workspace entry point returns the same plan's total, fa_debug_decode_plan (api.cpp) returns
-// it for tests/test_decode_host.py.
+// it for tests/test_decode_host.py.  decode_fp8_plan, below, is the same plan for the fp8 cache
+// (fa_decode_fp8.hip, fa_debug_decode_fp8_plan, tests/test_decode_fp8_host.py).
 #pragma once
 
 #include <algorithm>
@@ -75,6 +76,24 @@ inline DecodePlan decode_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64
 }
 
 int launch_decode_fwd(const DecodeArgs& a, hipStream_t s, const char** why);
+
+// The fp8 cache (fa_decode_fp8.hip, fa_decode_fp8_fwd): K and V are e4m3fn bytes, so a 16-B chunk
+// is 16 keys and the wide loads need Nk % 16 == 0.  Everything else is decode_plan's: the
+// same decode_nsplit, grid and workspace of fp32 partials (dtype is the type of Q and O).
+// kernel: kDecodeVec is decode8_fwd<.., VEC = true>, kDecodeNarrow its single-byte loads.
+inline DecodePlan decode_fp8_plan(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, int64_t group,
+                                  int force_nsplit, bool kv_aligned16) {
+    DecodePlan pl = decode_plan(dtype, N, Nk, d, dv, batch, group, force_nsplit, kv_aligned16);
+    if (pl.kernel != kDecodeNone) pl.kernel = Nk % 16 == 0 && kv_aligned16 ? kDecodeVec : kDecodeNarrow;
+    return pl;
+}
+
+struct DecodeFp8Args {
+    DecodeArgs a;                      // K, V: e4m3fn bytes; dtype: the type of Q and O
+    const float *k_scale, *v_scale;    // device, `batch` floats each, or nullptr (1.0)
+};
+
+int launch_decode_fp8_fwd(const DecodeFp8Args& a, hipStream_t s, const char** why);
 
 extern thread_local int g_decode_nsplit;   // fa_debug_set_decode_nsplit: 0 auto, n forces n key ranges
 

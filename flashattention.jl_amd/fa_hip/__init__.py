@@ -44,7 +44,7 @@ __all__ = [
     "causal_fa", "causal_fa_", "causal_fa_backward", "causal_dpa",
     "local_fa", "local_fa_", "local_fa_backward", "local_dpa",
     "varlen_fa", "varlen_fa_", "varlen_fa_backward", "varlen_dpa",
-    "decode_fa", "decode_fa_",
+    "decode_fa", "decode_fa_", "decode_fp8_fa", "decode_fp8_fa_", "quantize_kv_fp8",
     "fused_softmax", "fused_softmax_", "DTYPES",
 ]
 
@@ -202,6 +202,15 @@ def lib() -> ctypes.CDLL:
         L.fa_debug_decode_plan.restype = ctypes.c_int
         L.fa_debug_decode_plan.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64, i64, ctypes.c_int, ctypes.c_int,
                                            ctypes.POINTER(i64)]
+    if hasattr(L, "fa_decode_fp8_fwd"):
+        L.fa_decode_fp8_fwd_workspace.restype = ctypes.c_size_t
+        L.fa_decode_fp8_fwd_workspace.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64, i64]
+        L.fa_decode_fp8_fwd.restype = ctypes.c_int
+        L.fa_decode_fp8_fwd.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, vp, vp,
+                                        i64, i64, f32, vp, ctypes.c_size_t, vp]
+        L.fa_debug_decode_fp8_plan.restype = ctypes.c_int
+        L.fa_debug_decode_fp8_plan.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64, i64, ctypes.c_int, ctypes.c_int,
+                                               ctypes.POINTER(i64)]
     L.fa_softmax_workspace.restype = ctypes.c_size_t
     L.fa_softmax_workspace.argtypes = [i64, i64, i64, ctypes.c_int]
     L.fa_softmax.restype = ctypes.c_int
@@ -881,6 +890,102 @@ def decode_fa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k_lens=None, q_
     l = jl_empty((N, 1, BG), torch.float32, q.device)
     m = jl_empty((N, 1, BG), torch.float32, q.device)
     return decode_fa_(O, l, m, q, k, v, k_lens, q_lens, group, left, right, scale)
+
+
+# ----------------------------------------------------------------------------
+# decode over an fp8 cache: K and V as e4m3fn bytes plus one float32 scale per KV slab
+# (fa_decode_fp8_fwd; forward only)
+# ----------------------------------------------------------------------------
+_FP8_MAX = 448.0   # the largest e4m3fn value
+
+
+def _fp8_cache(t: torch.Tensor, name: str) -> torch.Tensor:
+    if t.dtype not in (torch.float8_e4m3fn, torch.uint8):
+        raise TypeError(f"{name} must be torch.float8_e4m3fn (or torch.uint8 holding the same bytes), got {t.dtype}")
+    return t
+
+
+def _kv_scale(s, B: int, device, name: str) -> Optional[torch.Tensor]:
+    """A scales argument as the C ABI takes it: None (1.0), or a float32 device tensor of shape
+    (B,), passed as it is (device data: nothing is read back).  A host sequence or CPU tensor is
+    checked to be finite and > 0 here (DimensionMismatch) and copied to the device."""
+    if s is None:
+        return None
+    if isinstance(s, torch.Tensor) and s.device.type == "cuda":
+        _require(s.dtype == torch.float32 and tuple(s.shape) == (B,) and s.is_contiguous(),
+                 f"DimensionMismatch: {name} must be a contiguous float32 tensor of shape ({B},)")
+        _require(s.device == device, "arrays on different devices")
+        return s
+    host = torch.as_tensor(s, device="cpu").to(torch.float32)
+    _require(host.dim() == 1 and host.numel() == B, f"DimensionMismatch: {name} must hold {B} scales")
+    _require(bool((torch.isfinite(host) & (host > 0)).all()), f"DimensionMismatch: {name} must be finite and > 0")
+    return host.to(device)
+
+
+def quantize_kv_fp8(k: torch.Tensor, v: torch.Tensor):
+    """``quantize_kv_fp8(k, v) -> (k8, v8, k_scale, v_scale)``: a (Nk, d, B) / (Nk, dv, B) cache as
+    e4m3fn with one float32 scale per slab, amax / 448 (1.0 where a slab is all zero), so that
+    ``k8.float() * k_scale`` is k rounded to the slab's fp8 grid.  Plain torch, any device."""
+    def one(t):
+        _require(t.dim() == 3, "quantize_kv_fp8 expects 3-D (Nk, d, batch) arrays")
+        amax = t.detach().abs().amax(dim=(0, 1)).to(torch.float32)
+        s = torch.where(amax > 0, amax / _FP8_MAX, torch.ones_like(amax))
+        q = (t.to(torch.float32) / s).clamp(-_FP8_MAX, _FP8_MAX)
+        t8 = jl_empty(t.shape, torch.float8_e4m3fn, t.device)
+        t8.copy_(q)
+        return t8, s.contiguous()
+    (k8, ks), (v8, vs) = one(k), one(v)
+    return k8, v8, ks, vs
+
+
+def decode_fp8_fa_(O: torch.Tensor, l: torch.Tensor, m: torch.Tensor,
+                   Q: torch.Tensor, K8: torch.Tensor, V8: torch.Tensor,
+                   k_scale=None, v_scale=None, k_lens=None, q_lens=None, group: int = 1,
+                   left: int = -1, right: int = 0, scale: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """:func:`decode_fa_` over an fp8 cache, in place.  K8 (Nk, d, B) and V8 (Nk, dv, B) are
+    ``torch.float8_e4m3fn`` (or ``torch.uint8`` holding the same bytes; anything else is a
+    TypeError); k_scale, v_scale: one float32 scale per KV slab (None: 1.0), finite and > 0.  The
+    result is decode_fa_'s on the dequantised cache ``K8 * k_scale[b]``, ``V8 * v_scale[b]``; Q, O
+    are bf16 / fp16, l, m float32."""
+    for t in (O, l, m, Q, K8, V8):
+        _require(t.dim() == 3, "decode_fp8_fa! expects 3-D (N, d, batch) arrays")
+    _fp8_cache(K8, "K8"), _fp8_cache(V8, "V8")
+    group = int(group)
+    _require(group >= 1, "DimensionMismatch: group must be >= 1")
+    N, d, BG = Q.shape
+    Nk, dv, B = K8.shape[0], V8.shape[1], K8.shape[2]
+    _require(BG == B * group, f"Q has batch {BG}, expected {B} KV slabs x group {group} = {B * group}")
+    _require(K8.shape == (Nk, d, B), f"K8 has shape {tuple(K8.shape)}, expected ({Nk}, {d}, {B})")
+    _require(V8.shape == (Nk, dv, B), f"V8 has shape {tuple(V8.shape)}, expected ({Nk}, {dv}, {B})")
+    _require(O.shape == (N, dv, BG), f"O has shape {tuple(O.shape)}, expected ({N}, {dv}, {BG})")
+    _require(l.shape == (N, 1, BG) and m.shape == (N, 1, BG), "l, m must be (N, 1, batch * group)")
+    _require(l.dtype == torch.float32 and m.dtype == torch.float32, "l, m must be float32")
+    code = _dtype_code(Q, O)
+    _masked_extents("decode", N, Nk)
+    _device_check(Q, K8, V8, O, l, m)
+    ql = _lens(q_lens, N, B, Q.device, "q_lens")
+    kl = _lens(k_lens, Nk, B, Q.device, "k_lens")
+    ks = _kv_scale(k_scale, B, Q.device, "k_scale")
+    vs = _kv_scale(v_scale, B, Q.device, "v_scale")
+    Lb = lib()
+    nws = Lb.fa_decode_fp8_fwd_workspace(code, N, Nk, d, dv, B, group)
+    ws = _workspace(Q.device, nws) if nws else None
+    _check(Lb.fa_decode_fp8_fwd(code, _ptr(Q), _ptr(K8), _ptr(V8), _ptr(ks), _ptr(vs), _ptr(O), _ptr(l), _ptr(m),
+                                N, Nk, d, dv, B, group, _ptr(ql), _ptr(kl), int(left), int(right), float(scale),
+                                _ptr(ws), int(nws), _stream(Q)))
+    return O, l, m
+
+
+def decode_fp8_fa(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, k_scale=None, v_scale=None, k_lens=None,
+                  q_lens=None, group: int = 1, left: int = -1, right: int = 0, scale: float = 0.0):
+    """``decode_fp8_fa(q, k8, v8, k_scale, v_scale, k_lens, q_lens, group, left, right) -> (O, l, m)``:
+    :func:`decode_fp8_fa_` on fresh outputs.  q (N, d, B*group), k8 (Nk, d, B), v8 (Nk, dv, B)."""
+    _require(q.dim() == 3 and k8.dim() == 3 and v8.dim() == 3, "decode_fp8_fa expects 3-D (N, d, batch) arrays")
+    N, _, BG = q.shape
+    O = jl_empty((N, v8.shape[1], BG), q.dtype, q.device)
+    l = jl_empty((N, 1, BG), torch.float32, q.device)
+    m = jl_empty((N, 1, BG), torch.float32, q.device)
+    return decode_fp8_fa_(O, l, m, q, k8, v8, k_scale, v_scale, k_lens, q_lens, group, left, right, scale)
 
 
 # ----------------------------------------------------------------------------

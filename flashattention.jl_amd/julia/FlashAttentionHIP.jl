@@ -547,6 +547,51 @@ function decode_fa(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3}; kw...) 
     return decode_fa!(O, l, m, Q, K, V; kw...)
 end
 
+# decode_fp8_fa!(O, l, m, Q, K8, V8; k_scale, v_scale, k_lens, q_lens, group, left, right) —
+# decode_fa! over an fp8 cache: K8 (Nk, d, B) and V8 (Nk, dv, B) hold OCP e4m3fn bytes as UInt8,
+# k_scale, v_scale one Float32 per KV slab (ROCArray{Float32,1} of length B, or `nothing`: 1.0),
+# finite and > 0, never read here.  The result is decode_fa!'s on the dequantised cache
+# K8 .* k_scale[b], V8 .* v_scale[b]; Q and O are BFloat16 / Float16.
+scale_ptr(::Nothing, B) = Ptr{Float32}(C_NULL)
+function scale_ptr(x::ROCArray{Float32,1}, B)
+    length(x) == B || throw(DimensionMismatch("scales must have one entry per KV slab"))
+    return Base.unsafe_convert(Ptr{Float32}, pointer(x))
+end
+
+function decode_fp8_fa!(O::ROCArray{T,3}, l::ROCArray{Float32,3}, m::ROCArray{Float32,3},
+                        Q::ROCArray{T,3}, K8::ROCArray{UInt8,3}, V8::ROCArray{UInt8,3};
+                        k_scale=nothing, v_scale=nothing, k_lens=nothing, q_lens=nothing, group::Integer=1,
+                        left::Integer=-1, right::Integer=0) where {T}
+    N, d, BG = size(Q)
+    Nk, dv, B = size(K8, 1), size(V8, 2), size(K8, 3)
+    group >= 1 && BG == B * group || throw(DimensionMismatch("Q must hold group query slabs per KV slab"))
+    size(K8) == (Nk, d, B) || throw(DimensionMismatch("K8"))
+    size(V8) == (Nk, dv, B) || throw(DimensionMismatch("V8"))
+    size(O) == (N, dv, BG) || throw(DimensionMismatch("O"))
+    size(l) == (N, 1, BG) && size(m) == (N, 1, BG) || throw(DimensionMismatch("l, m must be (N, 1, batch * group)"))
+    nws = ccall((:fa_decode_fp8_fwd_workspace, libfa_hip), Csize_t,
+                (Cint, Int64, Int64, Int64, Int64, Int64, Int64), fa_dtype(T), N, Nk, d, dv, B, group)
+    GC.@preserve q_lens k_lens k_scale v_scale with_workspace(nws) do ws
+        fa_check(ccall((:fa_decode_fp8_fwd, libfa_hip), Cint,
+                       (Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid}, Ptr{Float32},
+                        Ptr{Float32}, Int64, Int64, Int64, Int64, Int64, Int64, Ptr{Cint}, Ptr{Cint}, Int64, Int64, Cfloat,
+                        Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+                       fa_dtype(T), Q, K8, V8, scale_ptr(k_scale, B), scale_ptr(v_scale, B), O, l, m, N, Nk, d, dv, B,
+                       Int64(group), lens_ptr(q_lens, B), lens_ptr(k_lens, B), Int64(left), Int64(right), 0f0, ws, nws,
+                       stream_ptr()))
+    end
+    return O, l, m
+end
+
+# decode_fp8_fa(Q, K8, V8; k_scale, v_scale, k_lens, q_lens, group, left, right) -> (O, l, m)
+function decode_fp8_fa(Q::ROCArray{T,3}, K8::ROCArray{UInt8,3}, V8::ROCArray{UInt8,3}; kw...) where {T}
+    N, BG = size(Q, 1), size(Q, 3)
+    O = similar(Q, N, size(V8, 2), BG)
+    l = similar(Q, Float32, N, 1, BG)
+    m = similar(Q, Float32, N, 1, BG)
+    return decode_fp8_fa!(O, l, m, Q, K8, V8; kw...)
+end
+
 # varlen_fa_backward(Q, K, V, O, dO, l, m; q_lens, k_lens, left, right) -> (dQ, dK, dV): the
 # two-pass form, bitwise reproducible; exact zeros past the lengths and on empty rows
 function varlen_fa_backward(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3},

@@ -462,6 +462,41 @@ int fa_decode_fwd(int dtype,
 size_t fa_decode_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv,
                                int64_t batch, int64_t group);
 
+/* Decode attention over an fp8 KV cache: fa_decode_fwd with K and V stored as OCP e4m3fn bytes
+ * (max 448, NaN at 0x7F / 0xFF, no infinity) plus one float32 scale per KV slab.  `dtype` stays
+ * the type of Q and O (FA_DTYPE_BF16 or FA_DTYPE_F16); K8 is (Nk, d, batch) and V8
+ * (Nk, dv, batch) bytes.  k_scale and v_scale are DEVICE pointers to `batch` floats; NULL means
+ * 1.0.  With ks = k_scale[b], vs = v_scale[b] for KV slab b:
+ *   s_ij = scale * ks * (q_i . k8_j);   m, l over these scores in natural-log units, as above;
+ *   O = vs * sum_j P_ij v8_j.
+ * Every e4m3fn value is exact in bf16 and fp16, so the arithmetic after the convert is
+ * fa_decode_fwd's on the dequantised cache: ks is folded into the score scale and vs is applied
+ * once where O is normalised; no element is multiplied by a scale.  The scales are device data
+ * and are never read or validated on the host: they must be finite and > 0 (a non-positive ks
+ * would turn the row max into a min; the results are then meaningless, but no access depends
+ * on a scale).
+ * Shapes, the `group` mapping, the device lengths and their clamping, the mask as a select,
+ * the empty-row rule (O = +0, l = 0, m = -Inf), N * group <= 32, forward only, l and m float32
+ * are fa_decode_fwd's.  Padding rows of K8 / V8 may hold any byte except the two NaN encodings
+ * and change no output bit.
+ * Checks, in order, all before any launch, and the empty cases: as fa_decode_fwd, the 32-bit
+ * extents being a K8 / V8 slab below 2^31 bytes.  The cache is never copied: Nk % 16 != 0, or a
+ * K8 / V8 pointer that is not 16-B aligned, selects an instantiation with single-byte loads.
+ * The split over the keys, the merge order and the reproducibility are fa_decode_fwd's. */
+int fa_decode_fp8_fwd(int dtype,
+                      const void* Q, const void* K8, const void* V8,
+                      const float* k_scale, const float* v_scale,
+                      void* O, float* l, float* m,
+                      int64_t N, int64_t Nk, int64_t d, int64_t dv, int64_t batch, int64_t group,
+                      const int* q_lens, const int* k_lens,
+                      int64_t left, int64_t right,
+                      float scale, void* workspace, size_t workspace_bytes,
+                      void* hip_stream);
+
+/* Workspace bytes fa_decode_fp8_fwd needs: the same fp32 partials as fa_decode_fwd_workspace. */
+size_t fa_decode_fp8_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv,
+                                   int64_t batch, int64_t group);
+
 /* Standalone fused softmax, replaces
  *   fused_softmax!(P, S; dims)   reference src/fused_softmax.jl:1-41
  * (device versions src/cuda/fused_softmax.jl:11-314).  S, P: (M, N, batch)

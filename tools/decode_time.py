@@ -1,7 +1,7 @@
 """Decode attention against varlen attention on decode shapes: forward device time, one process,
 one run (tools/varlen_time.py's method).
 
-    python tools/decode_time.py [--window-s 0.05] [--windows 5]
+    python tools/decode_time.py [--window-s 0.05] [--windows 5] [--fp8]
 
 Per shape (bf16, d = dv = 128, the causal window (-1, 0), nq queries per slab, B KV slabs, G query
 heads per KV slab, a cache of Nk keys) and per draw of the cache lengths (all full; a fixed-seed
@@ -16,6 +16,12 @@ serves grouped heads; the repeat is made once, outside the timed region.
 Prints the median and the spread of each, their ratio, and the decode time as a multiple of the
 byte floor (sum_b nk_b) * (d + dv) * 2 B / 8 TB/s.  Asserts that decode_fa is faster than its
 baseline by more than the larger of the two spreads (max - min of the windows).
+
+--fp8 times the fp8 cache instead: fa_decode_fp8_fwd on quantize_kv_fp8's e4m3fn cache against
+fa_decode_fwd on the 16-bit dequantised copy of that same cache (k8 * k_scale rounded to bf16),
+same shapes, draws and method, outputs cross-checked.  Prints the ratio 16-bit / fp8 and the fp8
+time over its own floor (sum_b nk_b) * (d + dv) * 1 B / 8 TB/s, and says for each row whether fp8
+is faster by more than the larger spread; it asserts the cross-check only.
 """
 from __future__ import annotations
 
@@ -47,10 +53,66 @@ def window(fn, reps):
     return e0.elapsed_time(e1) * 1e-3 / reps
 
 
+def fp8_leg(a, L, g, code, left, right):
+    P = lambda t: ctypes.c_void_p(t.data_ptr())
+    dt = torch.bfloat16
+    print("fp8: fa_decode_fp8_fwd on the e4m3fn cache against fa_decode_fwd on its 16-bit dequantised copy", flush=True)
+    for (N, B, G, Nk) in SHAPES:
+        mk = lambda n, b: fa_hip.jl_tensor(torch.randn((n, D, b), generator=g, device="cuda"), dt)
+        Q, K, V = mk(N, B * G), mk(Nk, B), mk(Nk, B)
+        K8, V8, KS, VS = fa_hip.quantize_kv_fp8(K, V)
+        K.copy_(K8.float() * KS)   # the 16-bit leg's cache: the dequantised values, rounded to bf16
+        V.copy_(V8.float() * VS)
+        O, O8 = fa_hip.jl_empty((N, D, B * G), dt), fa_hip.jl_empty((N, D, B * G), dt)
+        l, m = fa_hip.jl_empty((N, 1, B * G)), fa_hip.jl_empty((N, 1, B * G))
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        nw = max(L.fa_decode_fwd_workspace(code, N, Nk, D, D, B, G), 1)
+        assert L.fa_decode_fp8_fwd_workspace(code, N, Nk, D, D, B, G) in (0, nw)
+        ws = torch.empty(nw, dtype=torch.uint8, device="cuda")
+        rnd = random.Random(7)
+        for name, kl in {"full": [Nk] * B, "uniform": [rnd.randint(Nk // 8, Nk) for _ in range(B)]}.items():
+            KL = torch.tensor(kl, dtype=torch.int32, device="cuda")
+
+            def dec():
+                rc = L.fa_decode_fwd(code, P(Q), P(K), P(V), P(O), P(l), P(m), N, Nk, D, D, B, G, None, P(KL), left, right,
+                                     0.0, P(ws), nw, st)
+                assert rc == 0, L.fa_last_error()
+
+            def dec8():
+                rc = L.fa_decode_fp8_fwd(code, P(Q), P(K8), P(V8), P(KS), P(VS), P(O8), P(l), P(m), N, Nk, D, D, B, G, None,
+                                         P(KL), left, right, 0.0, P(ws), nw, st)
+                assert rc == 0, L.fa_last_error()
+
+            runs = [("fp8", dec8), ("16-bit", dec)]
+            reps = {}
+            for nm, fn in runs:
+                for _ in range(2):
+                    fn()
+                torch.cuda.synchronize()
+                reps[nm] = max(3, min(20000, int(a.window_s / window(fn, 3)) + 1))
+            # the 16-bit cache is the fp8 one rounded once more (2^-9 relative): outputs agree to bf16 rounding
+            diff, top = float((O8.float() - O.float()).abs().max()), float(O.float().abs().max())
+            assert diff <= top / 64, f"fp8 and 16-bit outputs disagree: {diff} against max |O| {top}"
+            times = {nm: [] for nm, _ in runs}
+            for _ in range(a.windows):
+                for nm, fn in runs:
+                    times[nm].append(window(fn, reps[nm]))
+            med = {k: statistics.median(v) for k, v in times.items()}
+            spread = max(max(v) - min(v) for v in times.values())
+            floor = sum(kl) * 2 * D / HBM_BYTES_PER_S
+            print(f"nq {N} B {B:3d} G {G} Nk {Nk:5d} {name:7s}: fp8 {med['fp8']*1e6:9.1f} us "
+                  f"[{min(times['fp8'])*1e6:.1f}, {max(times['fp8'])*1e6:.1f}]  16-bit {med['16-bit']*1e6:9.1f} us "
+                  f"[{min(times['16-bit'])*1e6:.1f}, {max(times['16-bit'])*1e6:.1f}]  16-bit / fp8 {med['16-bit']/med['fp8']:5.2f}  "
+                  f"fp8 / its byte floor {med['fp8']/floor:6.2f}  max |dO| {diff:.2e}  "
+                  f"{'faster' if med['16-bit'] - med['fp8'] > spread else 'NOT FASTER than the spread'}", flush=True)
+        del Q, K, V, K8, V8
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--window-s", type=float, default=0.05)
     ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--fp8", action="store_true")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a ROCm device"
     L = fa_hip.lib()
@@ -60,8 +122,10 @@ def main():
     code = fa_hip.DTYPES[dt]
     left, right = -1, 0
     print(f"device: {torch.cuda.get_device_name(0)}; {a.windows} interleaved windows of {a.window_s} s; bf16, d = dv = {D}, "
-          f"window ({left}, {right}); the varlen baseline of G > 1 runs on a cache repeated G times outside the timed region",
-          flush=True)
+          f"window ({left}, {right})" + ("" if a.fp8 else
+          "; the varlen baseline of G > 1 runs on a cache repeated G times outside the timed region"), flush=True)
+    if a.fp8:
+        return fp8_leg(a, L, g, code, left, right)
     missed = []
     for (N, B, G, Nk) in SHAPES:
         mk = lambda n, b: fa_hip.jl_tensor(torch.randn((n, D, b), generator=g, device="cuda"), dt)
