@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "fa_common.h"
+#include "fa_decode_params.h"
 #include "fa_decode_plan.h"
 #include "fa_internal.h"
 #include "../../include/fa_hip.h"
@@ -37,19 +38,6 @@
 namespace fa {
 
 thread_local int g_decode_nsplit = 0;
-
-struct DecodeParams {
-    const void *Q, *K, *V;
-    void* O;
-    float *l, *m;
-    const int32_t *q_lens, *k_lens;
-    float* part;     // nsplit > 1: [nsplit][batch * group][N][dv + 2] = O (unnormalised), l, m (raw units)
-    int N, Nk, d, dv, batch, group, nsplit, total_wg;
-    int wleft, wright;   // mask_ints(kMaskVarlen)
-    float scale, scale_log2;
-};
-
-constexpr int kDecOobOff = 0x7FFFFFF0;   // a buffer offset past every slab: reads as 0
 
 // One 16-bit element at byte offset `off` of a slab, 0 where `ok` is false (VEC = false paths).
 __device__ __forceinline__ unsigned load16(__amdgpu_buffer_rsrc_t rs, bool ok, int off) {
@@ -79,28 +67,6 @@ __device__ __forceinline__ void decode_stage_k(__amdgpu_buffer_rsrc_t krs, char*
         } else {
             *(u32x4*)(buf + it * 1024 + lane * 16) = load8x16(krs, f < d, f * Nk, key0, Nk);
         }
-    }
-}
-
-// The empty state of the workgroup's rows: O = 0, l = 0, m = -inf (final, or as a partial).
-template <class T>
-__device__ __forceinline__ void decode_store_empty(const DecodeParams& p, int b, int sp) {
-    const int N = p.N, dv = p.dv, rows = N * p.group;
-    const int64_t R0 = (int64_t)b * rows;
-    if (p.nsplit == 1) {
-        T* const O = (T*)p.O;
-        for (int idx = threadIdx.x; idx < rows * dv; idx += kDecodeThreads) {
-            const int f = idx / rows, row = idx - f * rows, g = row / N, i = row - g * N;
-            O[(((int64_t)b * p.group + g) * dv + f) * N + i] = (T)0.0f;
-        }
-        for (int row = threadIdx.x; row < rows; row += kDecodeThreads) {
-            p.l[R0 + row] = 0.0f;
-            p.m[R0 + row] = kNegInf;
-        }
-    } else {
-        float* const part = p.part + ((int64_t)sp * p.batch * rows + R0) * (dv + 2);
-        for (int idx = threadIdx.x; idx < rows * (dv + 2); idx += kDecodeThreads)
-            part[idx] = idx % (dv + 2) == dv + 1 ? kNegInf : 0.0f;
     }
 }
 
@@ -384,6 +350,13 @@ __global__ __launch_bounds__(kDecodeThreads) void decode_combine(DecodeParams p,
         p.l[R] = live ? lsum : 0.0f;
         p.m[R] = live ? m * p.scale : kNegInf;
     }
+}
+
+void launch_decode_combine(int dtype, const DecodePlan& pl, const DecodeParams& p, hipStream_t s) {
+    const int64_t total = (int64_t)p.batch * p.group * p.N * p.dv;
+    const dim3 grid((unsigned)pl.combine_grid), blk(kDecodeThreads);
+    if (dtype == FA_DTYPE_F16) hipLaunchKernelGGL(decode_combine<f16>, grid, blk, 0, s, p, total);
+    else hipLaunchKernelGGL(decode_combine<bf16>, grid, blk, 0, s, p, total);
 }
 
 template <class T>

@@ -36,6 +36,8 @@ enum DecodeKernel : int {
     kDecodeNone = -1,     // refused (dtype, head dims, rows)
     kDecodeVec = 0,       // decode_fwd<.., VEC = true>: 16-B K DMA into LDS, 16-B V loads
     kDecodeNarrow = 1,    // decode_fwd<.., VEC = false>: 2-byte loads (Nk % 8 != 0 or misaligned K / V); no copies
+    kPagedTile = 2,       // decode_paged_fwd<.., TILE = true>: page_size % 64 == 0, a key tile lies in one page
+    kPagedChunk = 3,      // decode_paged_fwd<.., TILE = false>: page_size % 8 == 0, each 8-key chunk lies in one page
 };
 
 struct DecodePlan {
@@ -95,6 +97,28 @@ struct DecodeFp8Args {
 
 int launch_decode_fp8_fwd(const DecodeFp8Args& a, hipStream_t s, const char** why);
 
-extern thread_local int g_decode_nsplit;   // fa_debug_set_decode_nsplit: 0 auto, n forces n key ranges
+// The paged cache (fa_decode_paged.hip, fa_decode_paged_fwd): K and V are pools of pages of
+// page_size keys and a (max_pages, batch) table names each slab's pages.  The logical capacity
+// cap = max_pages * page_size is decode_plan's Nk for nsplit, grids and workspace; the kernel is
+// chosen by the page size alone (anything but a positive multiple of 8, or a cap past 32 bits,
+// is refused).  fa_debug_decode_paged_plan, tests/test_decode_paged_host.py.
+inline DecodePlan decode_paged_plan(int dtype, int64_t N, int64_t d, int64_t dv, int64_t batch, int64_t group,
+                                    int64_t page_size, int64_t max_pages, int force_nsplit) {
+    DecodePlan pl;
+    if (page_size < 8 || page_size % 8 != 0 || max_pages < 1 || max_pages > INT32_MAX / page_size) return pl;
+    pl = decode_plan(dtype, N, page_size * max_pages, d, dv, batch, group, force_nsplit, true);
+    if (pl.kernel != kDecodeNone) pl.kernel = page_size % kDecodeKeyTile == 0 ? kPagedTile : kPagedChunk;
+    return pl;
+}
+
+struct DecodePagedArgs {
+    DecodeArgs a;                  // K, V: the page pools; Nk: the logical capacity max_pages * page_size
+    const int32_t* block_table;    // device, (max_pages, batch)
+    int64_t page_size, num_pages, max_pages;
+};
+
+int launch_decode_paged_fwd(const DecodePagedArgs& a, hipStream_t s, const char** why);
+
+extern thread_local int g_decode_nsplit;  // fa_debug_set_decode_nsplit: 0 auto, n forces n key ranges
 
 }  // namespace fa

@@ -45,6 +45,7 @@ __all__ = [
     "local_fa", "local_fa_", "local_fa_backward", "local_dpa",
     "varlen_fa", "varlen_fa_", "varlen_fa_backward", "varlen_dpa",
     "decode_fa", "decode_fa_", "decode_fp8_fa", "decode_fp8_fa_", "quantize_kv_fp8",
+    "paged_decode_fa", "paged_decode_fa_", "paged_kv_gather",
     "fused_softmax", "fused_softmax_", "DTYPES",
 ]
 
@@ -211,6 +212,15 @@ def lib() -> ctypes.CDLL:
         L.fa_debug_decode_fp8_plan.restype = ctypes.c_int
         L.fa_debug_decode_fp8_plan.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64, i64, ctypes.c_int, ctypes.c_int,
                                                ctypes.POINTER(i64)]
+    if hasattr(L, "fa_decode_paged_fwd"):
+        L.fa_decode_paged_fwd_workspace.restype = ctypes.c_size_t
+        L.fa_decode_paged_fwd_workspace.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64, i64, i64]
+        L.fa_decode_paged_fwd.restype = ctypes.c_int
+        L.fa_decode_paged_fwd.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i64,
+                                          vp, vp, i64, i64, f32, vp, ctypes.c_size_t, vp]
+        L.fa_debug_decode_paged_plan.restype = ctypes.c_int
+        L.fa_debug_decode_paged_plan.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64, i64, i64, ctypes.c_int,
+                                                 ctypes.POINTER(i64)]
     L.fa_softmax_workspace.restype = ctypes.c_size_t
     L.fa_softmax_workspace.argtypes = [i64, i64, i64, ctypes.c_int]
     L.fa_softmax.restype = ctypes.c_int
@@ -986,6 +996,94 @@ def decode_fp8_fa(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, k_scale=N
     l = jl_empty((N, 1, BG), torch.float32, q.device)
     m = jl_empty((N, 1, BG), torch.float32, q.device)
     return decode_fp8_fa_(O, l, m, q, k8, v8, k_scale, v_scale, k_lens, q_lens, group, left, right, scale)
+
+
+# ----------------------------------------------------------------------------
+# decode over a paged cache: pools of pages of page_size keys and one page table per KV slab
+# (fa_decode_paged_fwd; forward only)
+# ----------------------------------------------------------------------------
+def _block_table(block_table, B: int, device) -> torch.Tensor:
+    _require(isinstance(block_table, torch.Tensor) and block_table.dim() == 2 and block_table.dtype == torch.int32,
+             "DimensionMismatch: block_table must be a 2-D (max_pages, batch) int32 tensor")
+    _require(block_table.shape[0] >= 1 and block_table.shape[1] == B,
+             f"block_table has shape {tuple(block_table.shape)}, expected (max_pages >= 1, {B})")
+    return block_table
+
+
+def paged_decode_fa_(O: torch.Tensor, l: torch.Tensor, m: torch.Tensor,
+                     Q: torch.Tensor, K_pages: torch.Tensor, V_pages: torch.Tensor, block_table: torch.Tensor,
+                     k_lens=None, q_lens=None, group: int = 1, left: int = -1, right: int = 0,
+                     scale: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """:func:`decode_fa_` over a paged cache, in place.  K_pages (page_size, d, num_pages) and
+    V_pages (page_size, dv, num_pages) are pools of pages; block_table (max_pages, B), int32 on
+    the device, column-major like every array here: entry (j, b) is the page holding logical keys
+    j * page_size .. of KV slab b.  The logical capacity max_pages * page_size stands where
+    decode_fa_ has Nk (k_lens are clamped to it).  The table is device data: only entries below
+    ceil(k_lens[b] / page_size) are read, each clamped to [0, num_pages); nothing is gathered.
+    page_size % 8 == 0, bf16 / fp16, N * group <= 32 (FlashAttentionError otherwise)."""
+    for t in (O, l, m, Q, K_pages, V_pages):
+        _require(t.dim() == 3, "paged_decode_fa! expects 3-D arrays: (N, d, batch) and (page_size, d, num_pages)")
+    group = int(group)
+    _require(group >= 1, "DimensionMismatch: group must be >= 1")
+    N, d, BG = Q.shape
+    ps, dv, P = K_pages.shape[0], V_pages.shape[1], K_pages.shape[2]
+    _require(BG % group == 0, f"Q has batch {BG}, not a multiple of group {group}")
+    B = BG // group
+    _require(ps >= 1 and P >= 1, "DimensionMismatch: page_size and num_pages must be >= 1")
+    _require(K_pages.shape == (ps, d, P), f"K_pages has shape {tuple(K_pages.shape)}, expected ({ps}, {d}, {P})")
+    _require(V_pages.shape == (ps, dv, P), f"V_pages has shape {tuple(V_pages.shape)}, expected ({ps}, {dv}, {P})")
+    bt = _block_table(block_table, B, Q.device)
+    max_pages = bt.shape[0]
+    _require(O.shape == (N, dv, BG), f"O has shape {tuple(O.shape)}, expected ({N}, {dv}, {BG})")
+    _require(l.shape == (N, 1, BG) and m.shape == (N, 1, BG), "l, m must be (N, 1, batch * group)")
+    _require(l.dtype == torch.float32 and m.dtype == torch.float32, "l, m must be float32")
+    code = _dtype_code(Q, K_pages, V_pages, O)
+    cap = max_pages * ps
+    _masked_extents("decode", N, cap)
+    _device_check(Q, K_pages, V_pages, O, l, m, bt)
+    ql = _lens(q_lens, N, B, Q.device, "q_lens")
+    kl = _lens(k_lens, cap, B, Q.device, "k_lens")
+    Lb = lib()
+    nws = Lb.fa_decode_paged_fwd_workspace(code, N, d, dv, B, group, ps, max_pages)
+    ws = _workspace(Q.device, nws) if nws else None
+    _check(Lb.fa_decode_paged_fwd(code, _ptr(Q), _ptr(K_pages), _ptr(V_pages), _ptr(bt), _ptr(O), _ptr(l), _ptr(m),
+                                  N, d, dv, B, group, ps, P, max_pages, _ptr(ql), _ptr(kl), int(left), int(right),
+                                  float(scale), _ptr(ws), int(nws), _stream(Q)))
+    return O, l, m
+
+
+def paged_decode_fa(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
+                    k_lens=None, q_lens=None, group: int = 1, left: int = -1, right: int = 0, scale: float = 0.0):
+    """``paged_decode_fa(q, k_pages, v_pages, block_table, k_lens, q_lens, group, left, right) ->
+    (O, l, m)``: :func:`paged_decode_fa_` on fresh outputs.  q (N, d, B*group), k_pages
+    (page_size, d, num_pages), v_pages (page_size, dv, num_pages), block_table (max_pages, B)."""
+    _require(q.dim() == 3 and k_pages.dim() == 3 and v_pages.dim() == 3,
+             "paged_decode_fa expects 3-D arrays: (N, d, batch) and (page_size, d, num_pages)")
+    N, _, BG = q.shape
+    O = jl_empty((N, v_pages.shape[1], BG), q.dtype, q.device)
+    l = jl_empty((N, 1, BG), torch.float32, q.device)
+    m = jl_empty((N, 1, BG), torch.float32, q.device)
+    return paged_decode_fa_(O, l, m, q, k_pages, v_pages, block_table, k_lens, q_lens, group, left, right, scale)
+
+
+def paged_kv_gather(k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor):
+    """``paged_kv_gather(k_pages, v_pages, block_table) -> (K, V)``: the contiguous
+    (max_pages * page_size, d, B) / (.., dv, B) slabs a page table describes, every entry
+    clamped to [0, num_pages) as the kernel clamps it.  Plain torch, any device: the naive form
+    (a full read and write of the cache), for :func:`decode_fa` or :func:`varlen_dpa`."""
+    _require(k_pages.dim() == 3 and v_pages.dim() == 3 and block_table.dim() == 2,
+             "paged_kv_gather expects (page_size, d, num_pages) pools and a (max_pages, batch) table")
+    _require(k_pages.shape[0] == v_pages.shape[0] and k_pages.shape[2] == v_pages.shape[2],
+             "k_pages and v_pages must agree in page_size and num_pages")
+    ps, _, P = k_pages.shape
+    max_pages, B = block_table.shape
+    idx = block_table.to(torch.int64).clamp(0, P - 1)                 # (max_pages, B)
+
+    def one(pool):
+        g = pool[:, :, idx]                                            # (ps, dim, max_pages, B)
+        slab = g.permute(2, 0, 1, 3).reshape(max_pages * ps, pool.shape[1], B)
+        return jl_tensor(slab, pool.dtype, pool.device)
+    return one(k_pages), one(v_pages)
 
 
 # ----------------------------------------------------------------------------

@@ -497,6 +497,52 @@ int fa_decode_fp8_fwd(int dtype,
 size_t fa_decode_fp8_fwd_workspace(int dtype, int64_t N, int64_t Nk, int64_t d, int64_t dv,
                                    int64_t batch, int64_t group);
 
+/* Decode attention over a PAGED KV cache: fa_decode_fwd with K and V kept as pools of fixed-size
+ * pages and one page table per KV slab, as serving stacks store a cache.  In the library's
+ * column-major convention K_pages is (page_size, d, num_pages), element (row t, feature f,
+ * page p) at t + page_size * (f + d * p), and V_pages is (page_size, dv, num_pages): a page is a
+ * small slab with keys contiguous per feature, exactly as a fa_decode_fwd slab.  block_table is
+ * a DEVICE array (max_pages, batch) of int32: entry (j, b), at j + max_pages * b, is the
+ * physical page that holds logical keys j * page_size .. (j + 1) * page_size - 1 of KV slab b.
+ * The logical capacity cap = max_pages * page_size plays the role of Nk everywhere in
+ * fa_decode_fwd's contract: the clamp of k_lens, off = nk - nq, windows >= cap are unbounded,
+ * cap >= N is required.  Q, O, l, m, `group`, q_lens, k_lens, the mask as a select, the
+ * empty-row rule (O = +0, l = 0, m = -Inf), N * group <= 32, bf16 / fp16 only, forward only are
+ * fa_decode_fwd's.
+ * The table is device data, never read or validated on the host.  The kernel reads entry
+ * (j, b) only for j < ceil(nk_b / page_size), and clamps every entry it dereferences to
+ * [0, num_pages) first: no access leaves the pools, whatever the table holds.  Entries at
+ * j >= ceil(nk_b / page_size) may hold anything; pages that no read entry names may hold any
+ * bit pattern, NaN included; rows of a slab's last page past nk_b may hold anything finite
+ * (fa_decode_fwd's padding rule); none of this changes an output bit.  Two slabs may name the
+ * same page (a shared prefix): pages are only read.
+ * Checks, in order, all before any launch: null pointers (block_table is required);
+ * DimensionMismatch (group, page_size, num_pages or max_pages below 1 included);
+ * FA_ERR_UNSUPPORTED for head dims, cap < N, N * group > 32, dtype, page_size % 8 != 0, K_pages
+ * or V_pages not 16-B aligned; the kernels' 32-bit extents (one page below 2^31 bytes, cap below
+ * 2^31; the pools have no size limit, page bases are 64-bit); the workspace.  N == 0 or
+ * batch == 0 is a no-op that dereferences nothing.
+ * The cache is never copied or gathered.  page_size % 64 == 0 runs the instantiation that builds
+ * one buffer descriptor per key tile from its table entry; every other multiple of 8 the one
+ * whose lanes look up the page of each 16-B chunk of 8 keys.  The split over the keys, the
+ * merge order and the reproducibility are fa_decode_fwd's, and the outputs do not depend on
+ * where in the pools the pages lie. */
+int fa_decode_paged_fwd(int dtype,
+                        const void* Q, const void* K_pages, const void* V_pages,
+                        const int* block_table,
+                        void* O, float* l, float* m,
+                        int64_t N, int64_t d, int64_t dv, int64_t batch, int64_t group,
+                        int64_t page_size, int64_t num_pages, int64_t max_pages,
+                        const int* q_lens, const int* k_lens,
+                        int64_t left, int64_t right,
+                        float scale, void* workspace, size_t workspace_bytes,
+                        void* hip_stream);
+
+/* Workspace bytes fa_decode_paged_fwd needs: fa_decode_fwd_workspace at Nk = max_pages *
+ * page_size (the fp32 partials of the key shares only). */
+size_t fa_decode_paged_fwd_workspace(int dtype, int64_t N, int64_t d, int64_t dv, int64_t batch,
+                                     int64_t group, int64_t page_size, int64_t max_pages);
+
 /* Standalone fused softmax, replaces
  *   fused_softmax!(P, S; dims)   reference src/fused_softmax.jl:1-41
  * (device versions src/cuda/fused_softmax.jl:11-314).  S, P: (M, N, batch)

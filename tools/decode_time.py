@@ -1,7 +1,7 @@
 """Decode attention against varlen attention on decode shapes: forward device time, one process,
 one run (tools/varlen_time.py's method).
 
-    python tools/decode_time.py [--window-s 0.05] [--windows 5] [--fp8]
+    python tools/decode_time.py [--window-s 0.05] [--windows 5] [--fp8 | --paged]
 
 Per shape (bf16, d = dv = 128, the causal window (-1, 0), nq queries per slab, B KV slabs, G query
 heads per KV slab, a cache of Nk keys) and per draw of the cache lengths (all full; a fixed-seed
@@ -22,6 +22,13 @@ fa_decode_fwd on the 16-bit dequantised copy of that same cache (k8 * k_scale ro
 same shapes, draws and method, outputs cross-checked.  Prints the ratio 16-bit / fp8 and the fp8
 time over its own floor (sum_b nk_b) * (d + dv) * 1 B / 8 TB/s, and says for each row whether fp8
 is faster by more than the larger spread; it asserts the cross-check only.
+
+--paged times the paged cache: fa_decode_paged_fwd at page sizes 16, 64 and 256 on pools the same
+cache was scattered into through shuffled page tables, against fa_decode_fwd on the contiguous
+cache and against gather-then-fa_decode_fwd (paged_kv_gather of the 64-key pool, then
+fa_decode_fwd: what a caller with a pool had to do), all in the same interleaved windows, same
+shapes and draws, without the nq = 4 row.  The paged outputs are cross-checked against the
+contiguous ones; nothing about the times is asserted.
 """
 from __future__ import annotations
 
@@ -108,11 +115,96 @@ def fp8_leg(a, L, g, code, left, right):
         del Q, K, V, K8, V8
 
 
+PAGE_SIZES = (16, 64, 256)
+
+
+def scatter(K, ps, g):
+    """A contiguous (Nk, d, B) cache as a pool (ps, d, Nk / ps * B) of pages in shuffled order and
+    its (Nk / ps, B) table."""
+    Nk, d, B = K.shape
+    mp = Nk // ps
+    pages = K.reshape(mp, ps, d, B).permute(1, 2, 0, 3).reshape(ps, d, mp * B)      # page j of slab b at j * B + b
+    perm = torch.randperm(mp * B, generator=g, device="cuda")
+    pool = fa_hip.jl_empty((ps, d, mp * B), K.dtype)
+    pool[:, :, perm] = pages
+    return pool, fa_hip.jl_tensor(perm.reshape(mp, B).to(torch.int32), torch.int32)
+
+
+def paged_leg(a, L, g, code, left, right):
+    P = lambda t: ctypes.c_void_p(t.data_ptr())
+    dt = torch.bfloat16
+    print("paged: fa_decode_paged_fwd at page sizes 16, 64, 256 (shuffled tables) against fa_decode_fwd on the contiguous "
+          "cache and against paged_kv_gather + fa_decode_fwd", flush=True)
+    for (N, B, G, Nk) in SHAPES:
+        if N != 1:
+            continue
+        mk = lambda n, b: fa_hip.jl_tensor(torch.randn((n, D, b), generator=g, device="cuda"), dt)
+        Q, K, V = mk(N, B * G), mk(Nk, B), mk(Nk, B)
+        pools = {}
+        for ps in PAGE_SIZES:
+            gp = torch.Generator(device="cuda").manual_seed(ps)
+            (KP, T), (VP, _) = scatter(K, ps, gp), scatter(V, ps, gp.manual_seed(ps))
+            pools[ps] = (KP, VP, T)
+        O = fa_hip.jl_empty((N, D, B * G), dt)
+        OP = {ps: fa_hip.jl_empty((N, D, B * G), dt) for ps in PAGE_SIZES}
+        OG = fa_hip.jl_empty((N, D, B * G), dt)
+        l, m = fa_hip.jl_empty((N, 1, B * G)), fa_hip.jl_empty((N, 1, B * G))
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        nw = max(L.fa_decode_fwd_workspace(code, N, Nk, D, D, B, G), 1)
+        for ps in PAGE_SIZES:
+            assert L.fa_decode_paged_fwd_workspace(code, N, D, D, B, G, ps, Nk // ps) in (0, nw)
+        ws = torch.empty(nw, dtype=torch.uint8, device="cuda")
+        rnd = random.Random(7)
+        for name, kl in {"full": [Nk] * B, "uniform": [rnd.randint(Nk // 8, Nk) for _ in range(B)]}.items():
+            KL = torch.tensor(kl, dtype=torch.int32, device="cuda")
+
+            def dec(Kc=K, Vc=V, Oc=O):
+                rc = L.fa_decode_fwd(code, P(Q), P(Kc), P(Vc), P(Oc), P(l), P(m), N, Nk, D, D, B, G, None, P(KL), left, right,
+                                     0.0, P(ws), nw, st)
+                assert rc == 0, L.fa_last_error()
+
+            def paged(ps):
+                KP, VP, T = pools[ps]
+                rc = L.fa_decode_paged_fwd(code, P(Q), P(KP), P(VP), P(T), P(OP[ps]), P(l), P(m), N, D, D, B, G, ps,
+                                           KP.shape[2], Nk // ps, None, P(KL), left, right, 0.0, P(ws), nw, st)
+                assert rc == 0, L.fa_last_error()
+
+            def gather():
+                Kg, Vg = fa_hip.paged_kv_gather(*pools[64])
+                dec(Kg, Vg, OG)
+
+            runs = [("contiguous", dec)] + [(f"page {ps}", (lambda ps=ps: paged(ps))) for ps in PAGE_SIZES] + [("gather", gather)]
+            reps = {}
+            for nm, fn in runs:
+                for _ in range(2):
+                    fn()
+                torch.cuda.synchronize()
+                reps[nm] = max(3, min(20000, int(a.window_s / window(fn, 3)) + 1))
+            top = float(O.float().abs().max())
+            same = []
+            for ps in PAGE_SIZES + ("gather",):
+                o = OG if ps == "gather" else OP[ps]
+                diff = float((o.float() - O.float()).abs().max())
+                assert diff <= top / 64, f"page {ps} and contiguous outputs disagree: {diff} against max |O| {top}"
+                same.append(bool(torch.equal(o, O)))
+            times = {nm: [] for nm, _ in runs}
+            for _ in range(a.windows):
+                for nm, fn in runs:
+                    times[nm].append(window(fn, reps[nm]))
+            med = {k: statistics.median(v) for k, v in times.items()}
+            cell = lambda nm: f"{nm} {med[nm]*1e6:8.1f} us [{min(times[nm])*1e6:.1f}, {max(times[nm])*1e6:.1f}]"
+            print(f"nq {N} B {B:3d} G {G} Nk {Nk:5d} {name:7s}: " + "  ".join(cell(nm) for nm, _ in runs) + "  paged / contiguous " +
+                  " ".join(f"{med[f'page {ps}']/med['contiguous']:5.2f}" for ps in PAGE_SIZES) +
+                  f"  gather / page 64 {med['gather']/med['page 64']:6.2f}  bitwise equal to contiguous {same}", flush=True)
+        del Q, K, V, pools
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--window-s", type=float, default=0.05)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--fp8", action="store_true")
+    ap.add_argument("--paged", action="store_true")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a ROCm device"
     L = fa_hip.lib()
@@ -122,10 +214,12 @@ def main():
     code = fa_hip.DTYPES[dt]
     left, right = -1, 0
     print(f"device: {torch.cuda.get_device_name(0)}; {a.windows} interleaved windows of {a.window_s} s; bf16, d = dv = {D}, "
-          f"window ({left}, {right})" + ("" if a.fp8 else
+          f"window ({left}, {right})" + ("" if a.fp8 or a.paged else
           "; the varlen baseline of G > 1 runs on a cache repeated G times outside the timed region"), flush=True)
     if a.fp8:
         return fp8_leg(a, L, g, code, left, right)
+    if a.paged:
+        return paged_leg(a, L, g, code, left, right)
     missed = []
     for (N, B, G, Nk) in SHAPES:
         mk = lambda n, b: fa_hip.jl_tensor(torch.randn((n, D, b), generator=g, device="cuda"), dt)
