@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "fa_common.h"
+#include "fa_decode8_params.h"
 #include "fa_decode_plan.h"
 #include "fa_internal.h"
 #include "../../include/fa_hip.h"
@@ -41,23 +42,6 @@
 namespace fa {
 
 namespace {
-
-struct Decode8Params {
-    const void* Q;
-    const uint8_t *K, *V;
-    const float *k_scale, *v_scale;   // `batch` floats each, or nullptr (1.0)
-    void* O;
-    float *l, *m;
-    const int32_t *q_lens, *k_lens;
-    float* part;     // nsplit > 1: [nsplit][batch * group][N][dv + 2] = O (unnormalised, unscaled), l, m (raw units)
-    int N, Nk, d, dv, batch, group, nsplit, total_wg;
-    int wleft, wright;   // mask_ints(kMaskVarlen)
-    float scale;
-};
-
-typedef int i32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int kDec8OobOff = 0x7FFFFFF0;   // a buffer offset past every slab: reads as 0
 
 // Four bytes from byte offset `off` of a slab, each 0 where `ok` is false or its key is past Nk
 // (the next row's bytes otherwise): the VEC = false loads.
@@ -67,31 +51,6 @@ __device__ __forceinline__ unsigned load4x8(__amdgpu_buffer_rsrc_t rs, bool ok, 
     for (int e = 0; e < 4; ++e)
         w |= (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rs, ok && key + e < Nk ? row + key + e : kDec8OobOff, 0, 0) << (8 * e);
     return w;
-}
-
-// Eight e4m3fn bytes (lo: elements 0..3, hi: 4..7) as one 16-bit MFMA operand; exact.
-template <class T>
-__device__ __forceinline__ typename Frag8<T>::type cvt8(unsigned lo, unsigned hi) {
-    if constexpr (std::is_same<T, bf16>::value) {
-        typedef __bf16 x2 __attribute__((ext_vector_type(2)));
-        const x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)lo, 1.0f, false);
-        const x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)lo, 1.0f, true);
-        const x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)hi, 1.0f, false);
-        const x2 d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)hi, 1.0f, true);
-        return bf16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
-    } else {
-        typedef _Float16 x2 __attribute__((ext_vector_type(2)));
-        const x2 a = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)lo, 1.0f, false);
-        const x2 b = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)lo, 1.0f, true);
-        const x2 c = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)hi, 1.0f, false);
-        const x2 d = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)hi, 1.0f, true);
-        return f16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
-    }
-}
-
-// ds_read_b64_tr_b8 (the lane mapping is in the file header)
-__device__ __forceinline__ i32x2 ds_read_tr8(const char* lds_ptr) {
-    return __builtin_amdgcn_ds_read_tr8_b64_v2i32((__attribute__((address_space(3))) i32x2*)(lds_void*)lds_ptr);
 }
 
 // One K tile into a wave's LDS image: 16-B chunk `it * 64 + lane` (byte it * 1024 + lane * 16) is
@@ -112,28 +71,6 @@ __device__ __forceinline__ void decode8_stage_k(__amdgpu_buffer_rsrc_t krs, char
             for (int j = 0; j < 4; ++j) w[j] = load4x8(krs, f < d, f * Nk, key0 + 4 * j, Nk);
             *(u32x4*)(buf + it * 1024 + lane * 16) = w;
         }
-    }
-}
-
-// The empty state of the workgroup's rows: O = 0, l = 0, m = -inf (final, or as a partial).
-template <class T>
-__device__ __forceinline__ void decode8_store_empty(const Decode8Params& p, int b, int sp) {
-    const int N = p.N, dv = p.dv, rows = N * p.group;
-    const int64_t R0 = (int64_t)b * rows;
-    if (p.nsplit == 1) {
-        T* const O = (T*)p.O;
-        for (int idx = threadIdx.x; idx < rows * dv; idx += kDecodeThreads) {
-            const int f = idx / rows, row = idx - f * rows, g = row / N, i = row - g * N;
-            O[(((int64_t)b * p.group + g) * dv + f) * N + i] = (T)0.0f;
-        }
-        for (int row = threadIdx.x; row < rows; row += kDecodeThreads) {
-            p.l[R0 + row] = 0.0f;
-            p.m[R0 + row] = kNegInf;
-        }
-    } else {
-        float* const part = p.part + ((int64_t)sp * p.batch * rows + R0) * (dv + 2);
-        for (int idx = threadIdx.x; idx < rows * (dv + 2); idx += kDecodeThreads)
-            part[idx] = idx % (dv + 2) == dv + 1 ? kNegInf : 0.0f;
     }
 }
 
@@ -451,6 +388,14 @@ hipError_t launch_decode8(const DecodePlan& pl, const Decode8Params& p, int Dc, 
 }
 
 }  // namespace
+
+// decode8_combine for the kernels of another file (fa_decode_paged_fp8.hip)
+void launch_decode8_combine(int dtype, const DecodePlan& pl, const Decode8Params& p, hipStream_t s) {
+    const int64_t total = (int64_t)p.batch * p.group * p.N * p.dv;
+    const dim3 grid((unsigned)pl.combine_grid), blk(kDecodeThreads);
+    if (dtype == FA_DTYPE_F16) hipLaunchKernelGGL(decode8_combine<f16>, grid, blk, 0, s, p, total);
+    else hipLaunchKernelGGL(decode8_combine<bf16>, grid, blk, 0, s, p, total);
+}
 
 int launch_decode_fp8_fwd(const DecodeFp8Args& a8, hipStream_t s, const char** why) {
     const DecodeArgs& a = a8.a;

@@ -38,6 +38,8 @@ enum DecodeKernel : int {
     kDecodeNarrow = 1,    // decode_fwd<.., VEC = false>: 2-byte loads (Nk % 8 != 0 or misaligned K / V); no copies
     kPagedTile = 2,       // decode_paged_fwd<.., TILE = true>: page_size % 64 == 0, a key tile lies in one page
     kPagedChunk = 3,      // decode_paged_fwd<.., TILE = false>: page_size % 8 == 0, each 8-key chunk lies in one page
+    kPaged8Tile = 4,      // decode_paged8_fwd<.., TILE = true>: fp8 pages, page_size % 64 == 0
+    kPaged8Chunk = 5,     // decode_paged8_fwd<.., TILE = false>: fp8 pages, page_size % 16 == 0, each 16-key chunk lies in one page
 };
 
 struct DecodePlan {
@@ -118,6 +120,27 @@ struct DecodePagedArgs {
 };
 
 int launch_decode_paged_fwd(const DecodePagedArgs& a, hipStream_t s, const char** why);
+
+// The paged fp8 cache (fa_decode_paged_fp8.hip, fa_decode_paged_fp8_fwd): pools of byte pages.
+// decode_plan at Nk = cap as decode_paged_plan; a 16-B chunk is 16 keys, so the page size must be
+// a positive multiple of 16.  fa_debug_decode_paged_fp8_plan, tests/test_decode_paged_fp8_host.py.
+inline DecodePlan decode_paged_fp8_plan(int dtype, int64_t N, int64_t d, int64_t dv, int64_t batch, int64_t group,
+                                        int64_t page_size, int64_t max_pages, int force_nsplit) {
+    DecodePlan pl;
+    if (page_size < 16 || page_size % 16 != 0 || max_pages < 1 || max_pages > INT32_MAX / page_size) return pl;
+    pl = decode_plan(dtype, N, page_size * max_pages, d, dv, batch, group, force_nsplit, true);
+    if (pl.kernel != kDecodeNone) pl.kernel = page_size % kDecodeKeyTile == 0 ? kPaged8Tile : kPaged8Chunk;
+    return pl;
+}
+
+struct DecodePagedFp8Args {
+    DecodeArgs a;                      // K, V: the byte page pools; Nk: the logical capacity; dtype: the type of Q and O
+    const float *k_scale, *v_scale;    // device, `batch` floats each, or nullptr (1.0)
+    const int32_t* block_table;        // device, (max_pages, batch)
+    int64_t page_size, num_pages, max_pages;
+};
+
+int launch_decode_paged_fp8_fwd(const DecodePagedFp8Args& a, hipStream_t s, const char** why);
 
 extern thread_local int g_decode_nsplit;  // fa_debug_set_decode_nsplit: 0 auto, n forces n key ranges
 

@@ -543,6 +543,56 @@ int fa_decode_paged_fwd(int dtype,
 size_t fa_decode_paged_fwd_workspace(int dtype, int64_t N, int64_t d, int64_t dv, int64_t batch,
                                      int64_t group, int64_t page_size, int64_t max_pages);
 
+/* Decode attention over a PAGED fp8 KV cache: fa_decode_paged_fwd's cache layout with
+ * fa_decode_fp8_fwd's element type, as a serving stack that keeps an fp8 cache stores it.
+ * K8_pages is (page_size, d, num_pages) and V8_pages (page_size, dv, num_pages) BYTES, OCP e4m3fn
+ * (max 448, NaN at 0x7F / 0xFF, no infinity), element (row t, feature f, page p) at
+ * t + page_size * (f + d * p); block_table is a DEVICE array (max_pages, batch) of int32 exactly
+ * as for fa_decode_paged_fwd, and cap = max_pages * page_size stands wherever fa_decode_fwd has
+ * Nk.  k_scale and v_scale are DEVICE pointers to `batch` floats, one per KV slab (not per page),
+ * NULL meaning 1.0, finite and > 0, never read or validated on the host: s_ij = scale * ks *
+ * (q_i . k8_j), O = vs * sum_j P_ij v8_j; ks is folded into the score scale and vs is applied
+ * once where O is normalised; no element is multiplied by a scale.  Two slabs may name the same
+ * page (a shared prefix; pages are only read); giving such slabs equal scales is the caller's
+ * business: each slab reads the page's bytes under its own scales.
+ * `dtype` is the type of Q and O (FA_DTYPE_BF16 or FA_DTYPE_F16).  Q, O, l, m, `group`, q_lens,
+ * k_lens, the mask as a select, the empty-row rule (O = +0, l = 0, m = -Inf), N * group <= 32 and
+ * forward only are fa_decode_fwd's.
+ * The table rules are fa_decode_paged_fwd's: entry (j, b) is read only for
+ * j < ceil(nk_b / page_size) and every entry is clamped to [0, num_pages) before it forms an
+ * address, so no access leaves the pools whatever the table holds.  Entries past that, and pages
+ * that no read entry names, may hold any byte, the two NaN encodings included.  Rows of a slab's
+ * last page past nk_b may hold any byte except 0x7F and 0xFF (fa_decode_fp8_fwd's padding rule).
+ * None of this changes an output bit.
+ * Checks, in order, all before any launch: null pointers (block_table is required; the scales
+ * may be NULL); DimensionMismatch (group, page_size, num_pages or max_pages below 1 included);
+ * FA_ERR_UNSUPPORTED for head dims, cap < N, N * group > 32, dtype, page_size % 16 != 0 (a 16-B
+ * chunk of 16 keys must lie in one page), K8_pages or V8_pages not 16-B aligned; the kernels'
+ * 32-bit extents (one page below 2^31 bytes, cap below 2^31; the pools have no size limit); the
+ * workspace.  N == 0 or batch == 0 is a no-op that dereferences nothing.
+ * The cache is never copied, gathered or widened.  page_size % 64 == 0 runs the instantiation
+ * that builds one buffer descriptor per key tile from its table entry; every other multiple of
+ * 16 the one whose lanes look up the page of each 16-B chunk of 16 keys.  The split over the
+ * keys, the merge order and the reproducibility are fa_decode_fwd's; the outputs do not depend
+ * on where in the pools the pages lie and are bitwise those of fa_decode_fp8_fwd on the gathered
+ * cache. */
+int fa_decode_paged_fp8_fwd(int dtype,
+                            const void* Q, const void* K8_pages, const void* V8_pages,
+                            const float* k_scale, const float* v_scale,
+                            const int* block_table,
+                            void* O, float* l, float* m,
+                            int64_t N, int64_t d, int64_t dv, int64_t batch, int64_t group,
+                            int64_t page_size, int64_t num_pages, int64_t max_pages,
+                            const int* q_lens, const int* k_lens,
+                            int64_t left, int64_t right,
+                            float scale, void* workspace, size_t workspace_bytes,
+                            void* hip_stream);
+
+/* Workspace bytes fa_decode_paged_fp8_fwd needs: fa_decode_fwd_workspace at Nk = max_pages *
+ * page_size (the fp32 partials of the key shares only). */
+size_t fa_decode_paged_fp8_fwd_workspace(int dtype, int64_t N, int64_t d, int64_t dv, int64_t batch,
+                                         int64_t group, int64_t page_size, int64_t max_pages);
+
 /* Standalone fused softmax, replaces
  *   fused_softmax!(P, S; dims)   reference src/fused_softmax.jl:1-41
  * (device versions src/cuda/fused_softmax.jl:11-314).  S, P: (M, N, batch)

@@ -1,7 +1,7 @@
 """Decode attention against varlen attention on decode shapes: forward device time, one process,
 one run (tools/varlen_time.py's method).
 
-    python tools/decode_time.py [--window-s 0.05] [--windows 5] [--fp8 | --paged]
+    python tools/decode_time.py [--window-s 0.05] [--windows 5] [--fp8 | --paged | --paged-fp8]
 
 Per shape (bf16, d = dv = 128, the causal window (-1, 0), nq queries per slab, B KV slabs, G query
 heads per KV slab, a cache of Nk keys) and per draw of the cache lengths (all full; a fixed-seed
@@ -29,6 +29,15 @@ cache and against gather-then-fa_decode_fwd (paged_kv_gather of the 64-key pool,
 fa_decode_fwd: what a caller with a pool had to do), all in the same interleaved windows, same
 shapes and draws, without the nq = 4 row.  The paged outputs are cross-checked against the
 contiguous ones; nothing about the times is asserted.
+
+--paged-fp8 times the paged fp8 cache: fa_decode_paged_fp8_fwd at page sizes 16, 64 and 256 on byte
+pools quantize_kv_fp8's cache was scattered into through shuffled page tables, against
+fa_decode_fp8_fwd on that contiguous fp8 cache (the cost of paging) and against fa_decode_paged_fwd
+on 16-bit pools of the dequantised cache scattered through the same tables (the gain from fp8), in
+the same interleaved windows, with --paged's shapes and draws.  The paged fp8 outputs are
+cross-checked against the contiguous fp8 ones (bitwise equality is reported) and the 16-bit ones
+to bf16 rounding; per page size it says whether fp8 is faster or slower than 16-bit by more than
+the larger of the two spreads, or a tie; nothing about the times is asserted.
 """
 from __future__ import annotations
 
@@ -199,12 +208,97 @@ def paged_leg(a, L, g, code, left, right):
         del Q, K, V, pools
 
 
+def paged_fp8_leg(a, L, g, code, left, right):
+    P = lambda t: ctypes.c_void_p(t.data_ptr())
+    dt = torch.bfloat16
+    print("paged fp8: fa_decode_paged_fp8_fwd at page sizes 16, 64, 256 (shuffled tables) against fa_decode_fp8_fwd on the "
+          "contiguous fp8 cache and against fa_decode_paged_fwd on the 16-bit pools of the same logical cache", flush=True)
+    for (N, B, G, Nk) in SHAPES:
+        if N != 1:
+            continue
+        mk = lambda n, b: fa_hip.jl_tensor(torch.randn((n, D, b), generator=g, device="cuda"), dt)
+        Q, K, V = mk(N, B * G), mk(Nk, B), mk(Nk, B)
+        K8, V8, KS, VS = fa_hip.quantize_kv_fp8(K, V)
+        K.copy_(K8.float() * KS)   # the 16-bit pools' cache: the dequantised values, rounded to bf16
+        V.copy_(V8.float() * VS)
+        pools8, pools16 = {}, {}
+        for ps in PAGE_SIZES:
+            for pools, (Kc, Vc) in ((pools8, (K8.view(torch.uint8), V8.view(torch.uint8))), (pools16, (K, V))):
+                gp = torch.Generator(device="cuda").manual_seed(ps)
+                (KP, T), (VP, _) = scatter(Kc, ps, gp), scatter(Vc, ps, gp.manual_seed(ps))
+                pools[ps] = (KP, VP, T)
+        mko = lambda: fa_hip.jl_empty((N, D, B * G), dt)
+        O8, OP8, OP16 = mko(), {ps: mko() for ps in PAGE_SIZES}, {ps: mko() for ps in PAGE_SIZES}
+        l, m = fa_hip.jl_empty((N, 1, B * G)), fa_hip.jl_empty((N, 1, B * G))
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        nw = max(L.fa_decode_fwd_workspace(code, N, Nk, D, D, B, G), 1)
+        for ps in PAGE_SIZES:
+            assert L.fa_decode_paged_fp8_fwd_workspace(code, N, D, D, B, G, ps, Nk // ps) in (0, nw)
+        ws = torch.empty(nw, dtype=torch.uint8, device="cuda")
+        rnd = random.Random(7)
+        for name, kl in {"full": [Nk] * B, "uniform": [rnd.randint(Nk // 8, Nk) for _ in range(B)]}.items():
+            KL = torch.tensor(kl, dtype=torch.int32, device="cuda")
+
+            def dec8():
+                rc = L.fa_decode_fp8_fwd(code, P(Q), P(K8), P(V8), P(KS), P(VS), P(O8), P(l), P(m), N, Nk, D, D, B, G, None,
+                                         P(KL), left, right, 0.0, P(ws), nw, st)
+                assert rc == 0, L.fa_last_error()
+
+            def paged8(ps):
+                KP, VP, T = pools8[ps]
+                rc = L.fa_decode_paged_fp8_fwd(code, P(Q), P(KP), P(VP), P(KS), P(VS), P(T), P(OP8[ps]), P(l), P(m), N, D, D, B,
+                                               G, ps, KP.shape[2], Nk // ps, None, P(KL), left, right, 0.0, P(ws), nw, st)
+                assert rc == 0, L.fa_last_error()
+
+            def paged16(ps):
+                KP, VP, T = pools16[ps]
+                rc = L.fa_decode_paged_fwd(code, P(Q), P(KP), P(VP), P(T), P(OP16[ps]), P(l), P(m), N, D, D, B, G, ps,
+                                           KP.shape[2], Nk // ps, None, P(KL), left, right, 0.0, P(ws), nw, st)
+                assert rc == 0, L.fa_last_error()
+
+            runs = ([("fp8 contiguous", dec8)] + [(f"fp8 page {ps}", (lambda ps=ps: paged8(ps))) for ps in PAGE_SIZES] +
+                    [(f"16-bit page {ps}", (lambda ps=ps: paged16(ps))) for ps in PAGE_SIZES])
+            reps = {}
+            for nm, fn in runs:
+                for _ in range(2):
+                    fn()
+                torch.cuda.synchronize()
+                reps[nm] = max(3, min(20000, int(a.window_s / window(fn, 3)) + 1))
+            # paged fp8 is the contiguous fp8 arithmetic on other addresses; the 16-bit cache is the fp8 one
+            # rounded once more (2^-9 relative)
+            top = float(O8.float().abs().max())
+            same = [bool(torch.equal(OP8[ps], O8)) for ps in PAGE_SIZES]
+            for ps in PAGE_SIZES:
+                for what, o in (("fp8", OP8[ps]), ("16-bit", OP16[ps])):
+                    diff = float((o.float() - O8.float()).abs().max())
+                    assert diff <= top / 64, f"{what} page {ps} and contiguous fp8 outputs disagree: {diff} against max |O| {top}"
+            times = {nm: [] for nm, _ in runs}
+            for _ in range(a.windows):
+                for nm, fn in runs:
+                    times[nm].append(window(fn, reps[nm]))
+            med = {k: statistics.median(v) for k, v in times.items()}
+            sp = {k: max(v) - min(v) for k, v in times.items()}
+            cell = lambda nm: f"{nm} {med[nm]*1e6:8.1f} us [{min(times[nm])*1e6:.1f}, {max(times[nm])*1e6:.1f}]"
+
+            def verdict(ps):   # fp8 against 16-bit at one page size: beyond the larger of the two spreads, or a tie
+                x, y = f"fp8 page {ps}", f"16-bit page {ps}"
+                gap = med[y] - med[x]
+                return "faster" if gap > max(sp[x], sp[y]) else "SLOWER" if -gap > max(sp[x], sp[y]) else "TIE"
+
+            print(f"nq {N} B {B:3d} G {G} Nk {Nk:5d} {name:7s}: " + "  ".join(cell(nm) for nm, _ in runs) +
+                  "  paged fp8 / contiguous fp8 " + " ".join(f"{med[f'fp8 page {ps}']/med['fp8 contiguous']:5.2f}" for ps in PAGE_SIZES) +
+                  "  paged 16-bit / paged fp8 " + " ".join(f"{med[f'16-bit page {ps}']/med[f'fp8 page {ps}']:5.2f}" for ps in PAGE_SIZES) +
+                  f"  fp8 against 16-bit {[verdict(ps) for ps in PAGE_SIZES]}  bitwise equal to contiguous fp8 {same}", flush=True)
+        del Q, K, V, K8, V8, pools8, pools16
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--window-s", type=float, default=0.05)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--fp8", action="store_true")
     ap.add_argument("--paged", action="store_true")
+    ap.add_argument("--paged-fp8", action="store_true")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a ROCm device"
     L = fa_hip.lib()
@@ -214,12 +308,14 @@ def main():
     code = fa_hip.DTYPES[dt]
     left, right = -1, 0
     print(f"device: {torch.cuda.get_device_name(0)}; {a.windows} interleaved windows of {a.window_s} s; bf16, d = dv = {D}, "
-          f"window ({left}, {right})" + ("" if a.fp8 or a.paged else
+          f"window ({left}, {right})" + ("" if a.fp8 or a.paged or a.paged_fp8 else
           "; the varlen baseline of G > 1 runs on a cache repeated G times outside the timed region"), flush=True)
     if a.fp8:
         return fp8_leg(a, L, g, code, left, right)
     if a.paged:
         return paged_leg(a, L, g, code, left, right)
+    if a.paged_fp8:
+        return paged_fp8_leg(a, L, g, code, left, right)
     missed = []
     for (N, B, G, Nk) in SHAPES:
         mk = lambda n, b: fa_hip.jl_tensor(torch.randn((n, D, b), generator=g, device="cuda"), dt)
