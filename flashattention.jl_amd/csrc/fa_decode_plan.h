@@ -142,6 +142,43 @@ struct DecodePagedFp8Args {
 
 int launch_decode_paged_fp8_fwd(const DecodePagedFp8Args& a, hipStream_t s, const char** why);
 
+// Chunked prefill over the paged cache (fa_prefill_paged.hip, fa_prefill_paged_fwd): decode_paged's
+// arguments with any N * group.  The rows of a KV slab, position-major, are cut into blocks of
+// kPrefillRows, one workgroup each; when batch * blocks is small each block's visible tile range
+// is cut into nsplit shares by decode_nsplit's rule, with batch * blocks where decode has batch.
+// The workspace and the combine grid are decode_plan's ([nsplit][batch * group][N][dv + 2] fp32),
+// the kernel is chosen by the page size alone.  fa_debug_prefill_paged_plan,
+// tests/test_prefill_paged_host.py.
+constexpr int kPrefillRows = 128;      // rows of a block: 4 waves, one 32-row MFMA tile each
+constexpr int kPrefillThreads = 256;
+constexpr DecodeKernel kPrefillTile = (DecodeKernel)6;    // prefill_paged_fwd<.., TILE = true>: page_size % 64 == 0, LDS-DMA staging
+constexpr DecodeKernel kPrefillChunk = (DecodeKernel)7;   // prefill_paged_fwd<.., TILE = false>: page_size % 8 == 0, 16-B chunks via registers
+
+struct PrefillPlan : DecodePlan {
+    int64_t blocks = 0;   // row blocks per KV slab; grid = batch * blocks * nsplit
+};
+
+inline PrefillPlan prefill_paged_plan(int dtype, int64_t N, int64_t d, int64_t dv, int64_t batch, int64_t group,
+                                      int64_t page_size, int64_t max_pages, int force_nsplit) {
+    PrefillPlan pl;
+    if (page_size < 8 || page_size % 8 != 0 || max_pages < 1 || max_pages > INT32_MAX / page_size) return pl;
+    const int64_t cap = page_size * max_pages;
+    if (!dense_16bit(dtype) || !head_dim_class(d) || !head_dim_class(dv) || N < 1 || group < 1 || batch < 1 || cap < N ||
+        group > INT32_MAX / N)
+        return pl;
+    pl.kernel = page_size % kDecodeKeyTile == 0 ? kPrefillTile : kPrefillChunk;
+    pl.blocks = ceil_div(N * group, kPrefillRows);
+    pl.nsplit = decode_nsplit(cap, batch * pl.blocks, force_nsplit);
+    pl.grid = batch * pl.blocks * pl.nsplit;
+    if (pl.nsplit > 1) {
+        pl.combine_grid = ceil_div(batch * group * N * dv, kDecodeThreads);
+        pl.total = (size_t)(pl.nsplit * batch * group * N * (dv + 2)) * sizeof(float) + 256;
+    }
+    return pl;
+}
+
+int launch_prefill_paged_fwd(const DecodePagedArgs& a, hipStream_t s, const char** why);
+
 extern thread_local int g_decode_nsplit;  // fa_debug_set_decode_nsplit: 0 auto, n forces n key ranges
 
 }  // namespace fa

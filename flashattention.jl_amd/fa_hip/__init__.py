@@ -46,6 +46,7 @@ __all__ = [
     "varlen_fa", "varlen_fa_", "varlen_fa_backward", "varlen_dpa",
     "decode_fa", "decode_fa_", "decode_fp8_fa", "decode_fp8_fa_", "quantize_kv_fp8",
     "paged_decode_fa", "paged_decode_fa_", "paged_kv_gather", "paged_decode_fp8_fa", "paged_decode_fp8_fa_",
+    "paged_prefill_fa", "paged_prefill_fa_",
     "fused_softmax", "fused_softmax_", "DTYPES",
 ]
 
@@ -230,6 +231,15 @@ def lib() -> ctypes.CDLL:
         L.fa_debug_decode_paged_fp8_plan.restype = ctypes.c_int
         L.fa_debug_decode_paged_fp8_plan.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64, i64, i64, ctypes.c_int,
                                                      ctypes.POINTER(i64)]
+    if hasattr(L, "fa_prefill_paged_fwd"):
+        L.fa_prefill_paged_fwd_workspace.restype = ctypes.c_size_t
+        L.fa_prefill_paged_fwd_workspace.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64, i64, i64]
+        L.fa_prefill_paged_fwd.restype = ctypes.c_int
+        L.fa_prefill_paged_fwd.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i64,
+                                           vp, vp, i64, i64, f32, vp, ctypes.c_size_t, vp]
+        L.fa_debug_prefill_paged_plan.restype = ctypes.c_int
+        L.fa_debug_prefill_paged_plan.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64, i64, i64, ctypes.c_int,
+                                                  ctypes.POINTER(i64)]
     L.fa_softmax_workspace.restype = ctypes.c_size_t
     L.fa_softmax_workspace.argtypes = [i64, i64, i64, ctypes.c_int]
     L.fa_softmax.restype = ctypes.c_int
@@ -1096,6 +1106,69 @@ def paged_kv_gather(k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: t
         out = jl_tensor(slab, slab.dtype, pool.device)
         return out.view(torch.float8_e4m3fn) if fp8 else out
     return one(k_pages), one(v_pages)
+
+
+# ----------------------------------------------------------------------------
+# chunked prefill over a paged cache: paged_decode_fa without the row limit
+# (fa_prefill_paged_fwd; forward only)
+# ----------------------------------------------------------------------------
+def paged_prefill_fa_(O: torch.Tensor, l: torch.Tensor, m: torch.Tensor,
+                      Q: torch.Tensor, K_pages: torch.Tensor, V_pages: torch.Tensor, block_table: torch.Tensor,
+                      k_lens=None, q_lens=None, group: int = 1, left: int = -1, right: int = 0,
+                      scale: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """:func:`paged_decode_fa_` for any N * group, in place: a chunked prefill (N new tokens
+    appended to a cached context, k_lens = context + N), a prefix-cache hit followed by the rest
+    of the prompt, or wide-group tree decoding.  The arguments, the mask, the empty-row rule and
+    the table rules are paged_decode_fa_'s: Q (N, d, B*group), K_pages (page_size, d, num_pages),
+    V_pages (page_size, dv, num_pages), block_table (max_pages, B) int32 on the device, query slab
+    bq reads KV slab bq // group; nothing is gathered and no K / V is repeated per query head.
+    page_size % 8 == 0, bf16 / fp16 (FlashAttentionError otherwise).
+    A contiguous (Nk, d, B) cache with Nk % 8 == 0 is the pool with page_size = Nk, num_pages = B
+    and block_table[0, b] = b, and runs through the same path: grouped-query prefill over a plain
+    cache without `group` copies of it."""
+    for t in (O, l, m, Q, K_pages, V_pages):
+        _require(t.dim() == 3, "paged_prefill_fa! expects 3-D arrays: (N, d, batch) and (page_size, d, num_pages)")
+    group = int(group)
+    _require(group >= 1, "DimensionMismatch: group must be >= 1")
+    N, d, BG = Q.shape
+    ps, dv, P = K_pages.shape[0], V_pages.shape[1], K_pages.shape[2]
+    _require(BG % group == 0, f"Q has batch {BG}, not a multiple of group {group}")
+    B = BG // group
+    _require(ps >= 1 and P >= 1, "DimensionMismatch: page_size and num_pages must be >= 1")
+    _require(K_pages.shape == (ps, d, P), f"K_pages has shape {tuple(K_pages.shape)}, expected ({ps}, {d}, {P})")
+    _require(V_pages.shape == (ps, dv, P), f"V_pages has shape {tuple(V_pages.shape)}, expected ({ps}, {dv}, {P})")
+    bt = _block_table(block_table, B, Q.device)
+    max_pages = bt.shape[0]
+    _require(O.shape == (N, dv, BG), f"O has shape {tuple(O.shape)}, expected ({N}, {dv}, {BG})")
+    _require(l.shape == (N, 1, BG) and m.shape == (N, 1, BG), "l, m must be (N, 1, batch * group)")
+    _require(l.dtype == torch.float32 and m.dtype == torch.float32, "l, m must be float32")
+    code = _dtype_code(Q, K_pages, V_pages, O)
+    cap = max_pages * ps
+    _masked_extents("prefill", N, cap)
+    _device_check(Q, K_pages, V_pages, O, l, m, bt)
+    ql = _lens(q_lens, N, B, Q.device, "q_lens")
+    kl = _lens(k_lens, cap, B, Q.device, "k_lens")
+    Lb = lib()
+    nws = Lb.fa_prefill_paged_fwd_workspace(code, N, d, dv, B, group, ps, max_pages)
+    ws = _workspace(Q.device, nws) if nws else None
+    _check(Lb.fa_prefill_paged_fwd(code, _ptr(Q), _ptr(K_pages), _ptr(V_pages), _ptr(bt), _ptr(O), _ptr(l), _ptr(m),
+                                   N, d, dv, B, group, ps, P, max_pages, _ptr(ql), _ptr(kl), int(left), int(right),
+                                   float(scale), _ptr(ws), int(nws), _stream(Q)))
+    return O, l, m
+
+
+def paged_prefill_fa(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
+                     k_lens=None, q_lens=None, group: int = 1, left: int = -1, right: int = 0, scale: float = 0.0):
+    """``paged_prefill_fa(q, k_pages, v_pages, block_table, k_lens, q_lens, group, left, right) ->
+    (O, l, m)``: :func:`paged_prefill_fa_` on fresh outputs.  q (N, d, B*group), k_pages
+    (page_size, d, num_pages), v_pages (page_size, dv, num_pages), block_table (max_pages, B)."""
+    _require(q.dim() == 3 and k_pages.dim() == 3 and v_pages.dim() == 3,
+             "paged_prefill_fa expects 3-D arrays: (N, d, batch) and (page_size, d, num_pages)")
+    N, _, BG = q.shape
+    O = jl_empty((N, v_pages.shape[1], BG), q.dtype, q.device)
+    l = jl_empty((N, 1, BG), torch.float32, q.device)
+    m = jl_empty((N, 1, BG), torch.float32, q.device)
+    return paged_prefill_fa_(O, l, m, q, k_pages, v_pages, block_table, k_lens, q_lens, group, left, right, scale)
 
 
 # ----------------------------------------------------------------------------

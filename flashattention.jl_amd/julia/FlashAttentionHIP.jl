@@ -634,6 +634,47 @@ function paged_decode_fa(Q::ROCArray{T,3}, K_pages::ROCArray{T,3}, V_pages::ROCA
     return paged_decode_fa!(O, l, m, Q, K_pages, V_pages, block_table; kw...)
 end
 
+# paged_prefill_fa!(O, l, m, Q, K_pages, V_pages, block_table; k_lens, q_lens, group, left, right) —
+# paged_decode_fa! for any N * group: a chunked prefill over the paged cache (N new tokens after a
+# cached context, k_lens = context + N), or wide-group tree decoding.  Arguments and table rules
+# as paged_decode_fa! (0-BASED page ids).  A contiguous (Nk, d, B) cache is the pool with
+# page_size = Nk and block_table = Int32[0 1 … B-1].
+function paged_prefill_fa!(O::ROCArray{T,3}, l::ROCArray{Float32,3}, m::ROCArray{Float32,3},
+                           Q::ROCArray{T,3}, K_pages::ROCArray{T,3}, V_pages::ROCArray{T,3},
+                           block_table::ROCArray{Int32,2};
+                           k_lens=nothing, q_lens=nothing, group::Integer=1, left::Integer=-1, right::Integer=0) where {T}
+    N, d, BG = size(Q)
+    ps, dv, P = size(K_pages, 1), size(V_pages, 2), size(K_pages, 3)
+    max_pages, B = size(block_table)
+    group >= 1 && BG == B * group || throw(DimensionMismatch("Q must hold group query slabs per KV slab"))
+    size(K_pages) == (ps, d, P) || throw(DimensionMismatch("K_pages"))
+    size(V_pages) == (ps, dv, P) || throw(DimensionMismatch("V_pages"))
+    size(O) == (N, dv, BG) || throw(DimensionMismatch("O"))
+    size(l) == (N, 1, BG) && size(m) == (N, 1, BG) || throw(DimensionMismatch("l, m must be (N, 1, batch * group)"))
+    nws = ccall((:fa_prefill_paged_fwd_workspace, libfa_hip), Csize_t,
+                (Cint, Int64, Int64, Int64, Int64, Int64, Int64, Int64), fa_dtype(T), N, d, dv, B, group, ps, max_pages)
+    GC.@preserve q_lens k_lens block_table with_workspace(nws) do ws
+        fa_check(ccall((:fa_prefill_paged_fwd, libfa_hip), Cint,
+                       (Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cint}, Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32},
+                        Int64, Int64, Int64, Int64, Int64, Int64, Int64, Int64, Ptr{Cint}, Ptr{Cint}, Int64, Int64, Cfloat,
+                        Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+                       fa_dtype(T), Q, K_pages, V_pages, Base.unsafe_convert(Ptr{Cint}, pointer(block_table)), O, l, m,
+                       N, d, dv, B, Int64(group), ps, P, max_pages, lens_ptr(q_lens, B), lens_ptr(k_lens, B),
+                       Int64(left), Int64(right), 0f0, ws, nws, stream_ptr()))
+    end
+    return O, l, m
+end
+
+# paged_prefill_fa(Q, K_pages, V_pages, block_table; k_lens, q_lens, group, left, right) -> (O, l, m)
+function paged_prefill_fa(Q::ROCArray{T,3}, K_pages::ROCArray{T,3}, V_pages::ROCArray{T,3},
+                          block_table::ROCArray{Int32,2}; kw...) where {T}
+    N, BG = size(Q, 1), size(Q, 3)
+    O = similar(Q, N, size(V_pages, 2), BG)
+    l = similar(Q, Float32, N, 1, BG)
+    m = similar(Q, Float32, N, 1, BG)
+    return paged_prefill_fa!(O, l, m, Q, K_pages, V_pages, block_table; kw...)
+end
+
 # paged_decode_fp8_fa!(O, l, m, Q, K8_pages, V8_pages, block_table; k_scale, v_scale, k_lens, q_lens,
 # group, left, right) — paged_decode_fa! over an fp8 cache: K8_pages (page_size, d, num_pages) and
 # V8_pages (page_size, dv, num_pages) hold OCP e4m3fn bytes as UInt8, block_table as for

@@ -593,6 +593,50 @@ int fa_decode_paged_fp8_fwd(int dtype,
 size_t fa_decode_paged_fp8_fwd_workspace(int dtype, int64_t N, int64_t d, int64_t dv, int64_t batch,
                                          int64_t group, int64_t page_size, int64_t max_pages);
 
+/* Chunked PREFILL attention over a paged KV cache: fa_decode_paged_fwd without its row limit, for
+ * a few hundred or thousand new tokens appended to a cached context (k_lens = context + N), a
+ * prefix-cache hit followed by the rest of the prompt, or tree decoding with wide groups.  Every
+ * argument, the layouts of Q, O, l, m, K_pages, V_pages and block_table, `group` (query slab bq
+ * reads KV slab bq / group), q_lens, k_lens (NULL: full), the mask (with off = nk - nq, query
+ * i < nq sees keys i + off - left <= j <= i + off + right, 0 <= j < nk; a negative side is
+ * unbounded), the empty-row rule (rows i >= nq and key-less queries: O = +0, l = 0, m = -Inf),
+ * cap = max_pages * page_size in the role of Nk, and the table rules (entry (j, b) read only for
+ * j < ceil(nk_b / page_size), clamped to [0, num_pages) before it forms an address; entries past
+ * that and pages no read entry names may hold anything; rows of a slab's last page past nk_b and
+ * padding rows of Q anything finite; shared pages allowed) are fa_decode_paged_fwd's.  N is any
+ * value >= 1 with cap >= N and group any value >= 1: N * group <= 32 is accepted too.  bf16 /
+ * fp16, d and dv up to 128, page_size any positive multiple of 8, forward only.
+ * A contiguous (Nk, d, batch) cache with Nk % 8 == 0 is the pool with page_size = Nk,
+ * num_pages = batch, max_pages = 1 and block_table[0, b] = b: grouped-query prefill over a plain
+ * cache, through the same kernels, without `group` copies of K and V.
+ * Checks, in order, all before any launch: null pointers (block_table is required);
+ * DimensionMismatch (group, page_size, num_pages or max_pages below 1 included);
+ * FA_ERR_UNSUPPORTED for head dims, cap < N, dtype, page_size % 8 != 0, K_pages or V_pages not
+ * 16-B aligned; the kernels' 32-bit extents (one page below 2^31 bytes, cap below 2^31, the
+ * N * group rows of a KV slab times max(d, dv) below 2^30 elements; the pools have no size
+ * limit); the workspace.  N == 0 or batch == 0 is a no-op that dereferences nothing.
+ * The cache is never copied, gathered or repeated.  The rows of a KV slab, position-major, are cut
+ * into blocks of 128 that share each key tile through LDS; page_size % 64 == 0 runs the
+ * instantiation that stages a tile by LDS-DMA through one descriptor per tile, every other
+ * multiple of 8 the one whose threads look up the page of each 16-B chunk.  Small grids split the
+ * keys (workspace: fp32 partials, merged in split order): no atomics, all three outputs bitwise
+ * reproducible and independent of where the pages lie, m the same bits for every split count. */
+int fa_prefill_paged_fwd(int dtype,
+                         const void* Q, const void* K_pages, const void* V_pages,
+                         const int* block_table,
+                         void* O, float* l, float* m,
+                         int64_t N, int64_t d, int64_t dv, int64_t batch, int64_t group,
+                         int64_t page_size, int64_t num_pages, int64_t max_pages,
+                         const int* q_lens, const int* k_lens,
+                         int64_t left, int64_t right,
+                         float scale, void* workspace, size_t workspace_bytes,
+                         void* hip_stream);
+
+/* Workspace bytes fa_prefill_paged_fwd needs: 0 unless the keys are split, then the fp32 partials
+ * [nsplit][batch * group][N][dv + 2] (+ 256). */
+size_t fa_prefill_paged_fwd_workspace(int dtype, int64_t N, int64_t d, int64_t dv, int64_t batch,
+                                      int64_t group, int64_t page_size, int64_t max_pages);
+
 /* Standalone fused softmax, replaces
  *   fused_softmax!(P, S; dims)   reference src/fused_softmax.jl:1-41
  * (device versions src/cuda/fused_softmax.jl:11-314).  S, P: (M, N, batch)

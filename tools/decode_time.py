@@ -1,7 +1,7 @@
 """Decode attention against varlen attention on decode shapes: forward device time, one process,
 one run (tools/varlen_time.py's method).
 
-    python tools/decode_time.py [--window-s 0.05] [--windows 5] [--fp8 | --paged | --paged-fp8]
+    python tools/decode_time.py [--window-s 0.05] [--windows 5] [--fp8 | --paged | --paged-fp8 | --prefill]
 
 Per shape (bf16, d = dv = 128, the causal window (-1, 0), nq queries per slab, B KV slabs, G query
 heads per KV slab, a cache of Nk keys) and per draw of the cache lengths (all full; a fixed-seed
@@ -38,6 +38,16 @@ the same interleaved windows, with --paged's shapes and draws.  The paged fp8 ou
 cross-checked against the contiguous fp8 ones (bitwise equality is reported) and the 16-bit ones
 to bf16 rounding; per page size it says whether fp8 is faster or slower than 16-bit by more than
 the larger of the two spreads, or a tie; nothing about the times is asserted.
+
+--prefill times chunked prefill over the paged cache: fa_prefill_paged_fwd with G = 8 on N in
+{8, 512, 2048} new tokens after a context of 8192 and 32768 keys (k_len = context + N), B in
+{1, 8}, page sizes 16 and 64, shuffled tables, against two yardsticks in the same interleaved
+windows: "today", what a caller with a pool has without it (paged_kv_gather, a G-fold repeat and
+fa_varlen_fwd, all timed), and "varlen alone", fa_varlen_fwd on a cache gathered and repeated
+outside the timed region.  Outputs are cross-checked.  Per row: median [min, max] of each, the
+two ratios, the achieved TFLOP/s of the new kernel and of varlen alone over the visible-pair
+FLOPs 2 (d + dv) B G (N context + N (N + 1) / 2), and whether the new path beats "today" by more
+than the sum of the two spreads (max - min); nothing about the times is asserted.
 """
 from __future__ import annotations
 
@@ -292,6 +302,77 @@ def paged_fp8_leg(a, L, g, code, left, right):
         del Q, K, V, K8, V8, pools8, pools16
 
 
+def prefill_leg(a, L, g, code, left, right):
+    P = lambda t: ctypes.c_void_p(t.data_ptr())
+    dt = torch.bfloat16
+    G = 8
+    print("prefill: fa_prefill_paged_fwd (G = 8, shuffled tables) against today = paged_kv_gather + G-fold repeat + fa_varlen_fwd "
+          "(all timed) and against fa_varlen_fwd alone on a cache gathered and repeated beforehand", flush=True)
+    for B in (1, 8):
+        for N in (8, 512, 2048):
+            for ctx in (8192, 32768):
+                for ps in (16, 64):
+                    nk = ctx + N
+                    mp = -(-nk // ps)
+                    cap = mp * ps
+                    mk = lambda n, b: fa_hip.jl_tensor(torch.randn((n, D, b), generator=g, device="cuda"), dt)
+                    Q, K, V = mk(N, B * G), mk(cap, B), mk(cap, B)
+                    gp = torch.Generator(device="cuda").manual_seed(ps)
+                    (KP, T), (VP, _) = scatter(K, ps, gp), scatter(V, ps, gp.manual_seed(ps))
+                    rep = lambda t: fa_hip.jl_tensor(t.repeat_interleave(G, dim=2), dt)
+                    KR, VR = rep(K), rep(V)
+                    mko = lambda: fa_hip.jl_empty((N, D, B * G), dt)
+                    O, OT, OV = mko(), mko(), mko()
+                    l, m = fa_hip.jl_empty((N, 1, B * G)), fa_hip.jl_empty((N, 1, B * G))
+                    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+                    nwp = max(L.fa_prefill_paged_fwd_workspace(code, N, D, D, B, G, ps, mp), 1)
+                    nwv = max(L.fa_varlen_fwd_workspace(code, N, cap, D, D, B * G), 1)
+                    wsp, wsv = torch.empty(nwp, dtype=torch.uint8, device="cuda"), torch.empty(nwv, dtype=torch.uint8, device="cuda")
+                    KL = torch.full((B,), nk, dtype=torch.int32, device="cuda")
+                    KLR = KL.repeat_interleave(G)
+
+                    def new():
+                        rc = L.fa_prefill_paged_fwd(code, P(Q), P(KP), P(VP), P(T), P(O), P(l), P(m), N, D, D, B, G, ps,
+                                                    KP.shape[2], mp, None, P(KL), left, right, 0.0, P(wsp), nwp, st)
+                        assert rc == 0, L.fa_last_error()
+
+                    def var(Kc=KR, Vc=VR, Oc=OV):
+                        rc = L.fa_varlen_fwd(code, P(Q), P(Kc), P(Vc), P(Oc), P(l), P(m), N, cap, D, D, B * G, None, P(KLR), left,
+                                             right, 0.0, P(wsv), nwv, st)
+                        assert rc == 0, L.fa_last_error()
+
+                    def today():
+                        Kg, Vg = fa_hip.paged_kv_gather(KP, VP, T)
+                        var(rep(Kg), rep(Vg), OT)
+
+                    runs = [("new", new), ("today", today), ("varlen alone", var)]
+                    reps = {}
+                    for nm, fn in runs:
+                        for _ in range(2):
+                            fn()
+                        torch.cuda.synchronize()
+                        reps[nm] = max(3, min(20000, int(a.window_s / window(fn, 3)) + 1))
+                    top = float(OV.float().abs().max())
+                    for what, o in (("new", O), ("today", OT)):
+                        diff = float((o.float() - OV.float()).abs().max())
+                        assert diff <= top / 64, f"{what} and varlen outputs disagree: {diff} against max |O| {top}"
+                    times = {nm: [] for nm, _ in runs}
+                    for _ in range(a.windows):
+                        for nm, fn in runs:
+                            times[nm].append(window(fn, reps[nm]))
+                    med = {k: statistics.median(v) for k, v in times.items()}
+                    sp = {k: max(v) - min(v) for k, v in times.items()}
+                    flops = 2.0 * (D + D) * B * G * (N * ctx + N * (N + 1) / 2)
+                    cell = lambda nm: f"{nm} {med[nm]*1e6:9.1f} us [{min(times[nm])*1e6:.1f}, {max(times[nm])*1e6:.1f}]"
+                    beats = med["today"] - med["new"] > sp["today"] + sp["new"]
+                    print(f"B {B} N {N:4d} context {ctx:5d} page {ps:2d}: " + "  ".join(cell(nm) for nm, _ in runs) +
+                          f"  today / new {med['today']/med['new']:7.2f}  varlen alone / new {med['varlen alone']/med['new']:5.2f}  "
+                          f"TFLOP/s new {flops/med['new']*1e-12:6.1f} varlen alone {flops/med['varlen alone']*1e-12:6.1f}  "
+                          f"{'beats today by more than the spreads' if beats else 'DOES NOT BEAT today by more than the spreads'}",
+                          flush=True)
+                    del Q, K, V, KP, VP, KR, VR
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--window-s", type=float, default=0.05)
@@ -299,6 +380,7 @@ def main():
     ap.add_argument("--fp8", action="store_true")
     ap.add_argument("--paged", action="store_true")
     ap.add_argument("--paged-fp8", action="store_true")
+    ap.add_argument("--prefill", action="store_true")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a ROCm device"
     L = fa_hip.lib()
@@ -308,7 +390,7 @@ def main():
     code = fa_hip.DTYPES[dt]
     left, right = -1, 0
     print(f"device: {torch.cuda.get_device_name(0)}; {a.windows} interleaved windows of {a.window_s} s; bf16, d = dv = {D}, "
-          f"window ({left}, {right})" + ("" if a.fp8 or a.paged or a.paged_fp8 else
+          f"window ({left}, {right})" + ("" if a.fp8 or a.paged or a.paged_fp8 or a.prefill else
           "; the varlen baseline of G > 1 runs on a cache repeated G times outside the timed region"), flush=True)
     if a.fp8:
         return fp8_leg(a, L, g, code, left, right)
@@ -316,6 +398,8 @@ def main():
         return paged_leg(a, L, g, code, left, right)
     if a.paged_fp8:
         return paged_fp8_leg(a, L, g, code, left, right)
+    if a.prefill:
+        return prefill_leg(a, L, g, code, left, right)
     missed = []
     for (N, B, G, Nk) in SHAPES:
         mk = lambda n, b: fa_hip.jl_tensor(torch.randn((n, D, b), generator=g, device="cuda"), dt)
