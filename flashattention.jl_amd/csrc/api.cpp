@@ -946,6 +946,71 @@ int fa_prefill_paged_fwd(int dtype, const void* Q, const void* K_pages, const vo
     return rc == FA_OK ? ok() : fail(rc, fn, why);
 }
 
+// Chunked prefill over a paged fp8 cache (fa_prefill_paged_fp8.hip): fa_prefill_paged_fwd's checks
+// in its order, with bytes where it has 16-bit elements, page_size % 16 in the place of % 8 and
+// fa_decode_paged_fp8_fwd's optional scales; the table and the scales are device data and are not
+// looked at here.  fa_debug_set_decode_nsplit governs this entry point too.
+
+// Not part of the public header (tests): fa::prefill_paged_fp8_plan, as fa_debug_prefill_paged_plan.
+int fa_debug_prefill_paged_fp8_plan(int dtype, int64_t N, int64_t d, int64_t dv, int64_t batch, int64_t group,
+                                    int64_t page_size, int64_t max_pages, int force_nsplit, int64_t* out) {
+    const fa::PrefillPlan pl = fa::prefill_paged_fp8_plan(dtype, N, d, dv, batch, group, page_size, max_pages, force_nsplit);
+    if (out) {
+        out[0] = pl.kernel; out[1] = pl.nsplit; out[2] = pl.grid; out[3] = (int64_t)pl.total; out[4] = pl.blocks;
+    }
+    return pl.kernel;
+}
+
+size_t fa_prefill_paged_fp8_fwd_workspace(int dtype, int64_t N, int64_t d, int64_t dv, int64_t batch, int64_t group,
+                                          int64_t page_size, int64_t max_pages) {
+    return fa::prefill_paged_fp8_plan(dtype, N, d, dv, batch, group, page_size, max_pages, fa::g_decode_nsplit).total;
+}
+
+int fa_prefill_paged_fp8_fwd(int dtype, const void* Q, const void* K8_pages, const void* V8_pages, const float* k_scale,
+                             const float* v_scale, const int32_t* block_table, void* O, float* l, float* m, int64_t N,
+                             int64_t d, int64_t dv, int64_t batch, int64_t group, int64_t page_size, int64_t num_pages,
+                             int64_t max_pages, const int32_t* q_lens, const int32_t* k_lens, int64_t left, int64_t right,
+                             float scale, void* workspace, size_t workspace_bytes, void* hip_stream) {
+    const char* const fn = "fa_prefill_paged_fp8_fwd";
+    if (!valid_dtype(dtype)) return fail(FA_ERR_INVALID_ARG, fn, "unknown dtype");
+    if (N == 0 || batch == 0) return ok();   // no query: nothing to write, nothing dereferenced
+    if (!Q || !K8_pages || !V8_pages || !block_table || !O || !l || !m) return fail(FA_ERR_INVALID_ARG, fn, "null pointer");
+    if (N < 0 || d < 1 || dv < 1 || batch < 0 || group < 1 || page_size < 1 || num_pages < 1 || max_pages < 1)
+        return fail(FA_ERR_INVALID_ARG, fn,
+                    "DimensionMismatch: N, batch must be >= 0 and d, dv, group, page_size, num_pages, max_pages >= 1");
+    if (d > fa::kMaxHeadDim || dv > fa::kMaxHeadDim)
+        return fail(FA_ERR_UNSUPPORTED, fn, "head dimension exceeds the compiled maximum (128)");
+    // cap = max_pages * page_size, saturated: the 32-bit check below refuses what would overflow
+    const int64_t cap = max_pages > INT64_MAX / page_size ? INT64_MAX : max_pages * page_size;
+    if (cap < N)
+        return fail(FA_ERR_UNSUPPORTED, fn, "prefill attention needs max_pages * page_size >= N (a query would see no key)");
+    if (!fa::dense_16bit(dtype))
+        return fail(FA_ERR_UNSUPPORTED, fn, "paged fp8 prefill attention is bf16 / fp16 only (Q and O; the cache is e4m3fn)");
+    if (page_size % 16 != 0)
+        return fail(FA_ERR_UNSUPPORTED, fn,
+                    "paged fp8 prefill attention needs page_size % 16 == 0 (a 16-B chunk of 16 keys lies in one page)");
+    if (!fa::aligned16(K8_pages) || !fa::aligned16(V8_pages))
+        return fail(FA_ERR_UNSUPPORTED, fn, "paged fp8 prefill attention needs 16-B aligned K8_pages and V8_pages");
+    // one page of bytes, and the N * group rows of a KV slab in Q and O, within the descriptors'
+    // 32-bit byte offsets; the logical keys (and one key tile past them) within an int; the pools
+    // have no limit: page bases are 64-bit
+    const int64_t dmax = d > dv ? d : dv;
+    if (page_size > INT32_MAX || page_size * dmax >= (int64_t)INT32_MAX || cap > INT32_MAX - 2 * fa::kDecodeKeyTile ||
+        batch * group > INT32_MAX / 64 || group > INT32_MAX / N || N * group >= (int64_t)INT32_MAX / (2 * dmax))
+        return fail(FA_ERR_UNSUPPORTED, fn, "extent exceeds the kernels' 32-bit addressing");
+    const fa::PrefillPlan pl = fa::prefill_paged_fp8_plan(dtype, N, d, dv, batch, group, page_size, max_pages, fa::g_decode_nsplit);
+    if (pl.grid > INT32_MAX || pl.combine_grid > INT32_MAX)
+        return fail(FA_ERR_UNSUPPORTED, fn, "extent exceeds the kernels' 32-bit addressing");
+    if (pl.total > 0 && (!workspace || workspace_bytes < pl.total))
+        return fail(FA_ERR_WORKSPACE, fn, "workspace missing or smaller than fa_prefill_paged_fp8_fwd_workspace()");
+    fa::DecodePagedFp8Args a{{dtype, Q, K8_pages, V8_pages, O, l, m, N, cap, d, dv, batch, group, q_lens, k_lens, left, right,
+                              resolve_scale(scale, d), workspace, workspace_bytes},
+                             k_scale, v_scale, block_table, page_size, num_pages, max_pages};
+    const char* why = "";
+    const int rc = fa::launch_prefill_paged_fp8_fwd(a, (hipStream_t)hip_stream, &why);
+    return rc == FA_OK ? ok() : fail(rc, fn, why);
+}
+
 // Not part of the public header: launch order of the causal fast forward's query blocks
 // 0 in order; 1 slab by slab, a slab's heaviest (last) block first; 2 block-major inside each
 // XCD's share of the grid, heaviest blocks of all its slabs first (where that share holds

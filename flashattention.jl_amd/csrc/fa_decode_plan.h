@@ -179,6 +179,23 @@ inline PrefillPlan prefill_paged_plan(int dtype, int64_t N, int64_t d, int64_t d
 
 int launch_prefill_paged_fwd(const DecodePagedArgs& a, hipStream_t s, const char** why);
 
+// Chunked prefill over the paged fp8 cache (fa_prefill_paged_fp8.hip, fa_prefill_paged_fp8_fwd):
+// prefill_paged_plan over pools of byte pages.  A 16-B chunk is 16 keys, so the page size must be a
+// positive multiple of 16; blocks, nsplit, grids and workspace are prefill_paged_plan's (dtype is
+// the type of Q and O).  fa_debug_prefill_paged_fp8_plan, tests/test_prefill_paged_fp8_host.py.
+constexpr DecodeKernel kPrefill8Tile = (DecodeKernel)8;    // prefill_paged8_fwd<.., TILE = true>: page_size % 64 == 0, LDS-DMA staging
+constexpr DecodeKernel kPrefill8Chunk = (DecodeKernel)9;   // prefill_paged8_fwd<.., TILE = false>: page_size % 16 == 0, 16-B chunks via registers
+
+inline PrefillPlan prefill_paged_fp8_plan(int dtype, int64_t N, int64_t d, int64_t dv, int64_t batch, int64_t group,
+                                          int64_t page_size, int64_t max_pages, int force_nsplit) {
+    if (page_size % 16 != 0) return PrefillPlan();
+    PrefillPlan pl = prefill_paged_plan(dtype, N, d, dv, batch, group, page_size, max_pages, force_nsplit);
+    if (pl.kernel != kDecodeNone) pl.kernel = pl.kernel == kPrefillTile ? kPrefill8Tile : kPrefill8Chunk;
+    return pl;
+}
+
+int launch_prefill_paged_fp8_fwd(const DecodePagedFp8Args& a, hipStream_t s, const char** why);
+
 extern thread_local int g_decode_nsplit;  // fa_debug_set_decode_nsplit: 0 auto, n forces n key ranges
 
 }  // namespace fa

@@ -46,7 +46,7 @@ __all__ = [
     "varlen_fa", "varlen_fa_", "varlen_fa_backward", "varlen_dpa",
     "decode_fa", "decode_fa_", "decode_fp8_fa", "decode_fp8_fa_", "quantize_kv_fp8",
     "paged_decode_fa", "paged_decode_fa_", "paged_kv_gather", "paged_decode_fp8_fa", "paged_decode_fp8_fa_",
-    "paged_prefill_fa", "paged_prefill_fa_",
+    "paged_prefill_fa", "paged_prefill_fa_", "paged_prefill_fp8_fa", "paged_prefill_fp8_fa_",
     "fused_softmax", "fused_softmax_", "DTYPES",
 ]
 
@@ -240,6 +240,15 @@ def lib() -> ctypes.CDLL:
         L.fa_debug_prefill_paged_plan.restype = ctypes.c_int
         L.fa_debug_prefill_paged_plan.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64, i64, i64, ctypes.c_int,
                                                   ctypes.POINTER(i64)]
+    if hasattr(L, "fa_prefill_paged_fp8_fwd"):
+        L.fa_prefill_paged_fp8_fwd_workspace.restype = ctypes.c_size_t
+        L.fa_prefill_paged_fp8_fwd_workspace.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64, i64, i64]
+        L.fa_prefill_paged_fp8_fwd.restype = ctypes.c_int
+        L.fa_prefill_paged_fp8_fwd.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64,
+                                               i64, i64, vp, vp, i64, i64, f32, vp, ctypes.c_size_t, vp]
+        L.fa_debug_prefill_paged_fp8_plan.restype = ctypes.c_int
+        L.fa_debug_prefill_paged_fp8_plan.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64, i64, i64, ctypes.c_int,
+                                                      ctypes.POINTER(i64)]
     L.fa_softmax_workspace.restype = ctypes.c_size_t
     L.fa_softmax_workspace.argtypes = [i64, i64, i64, ctypes.c_int]
     L.fa_softmax.restype = ctypes.c_int
@@ -1234,6 +1243,75 @@ def paged_decode_fp8_fa(q: torch.Tensor, k8_pages: torch.Tensor, v8_pages: torch
     m = jl_empty((N, 1, BG), torch.float32, q.device)
     return paged_decode_fp8_fa_(O, l, m, q, k8_pages, v8_pages, block_table, k_scale, v_scale, k_lens, q_lens, group,
                                 left, right, scale)
+
+
+# ----------------------------------------------------------------------------
+# chunked prefill over a paged fp8 cache: paged_decode_fp8_fa without the row limit
+# (fa_prefill_paged_fp8_fwd; forward only)
+# ----------------------------------------------------------------------------
+def paged_prefill_fp8_fa_(O: torch.Tensor, l: torch.Tensor, m: torch.Tensor,
+                          Q: torch.Tensor, K8_pages: torch.Tensor, V8_pages: torch.Tensor, block_table: torch.Tensor,
+                          k_scale=None, v_scale=None, k_lens=None, q_lens=None, group: int = 1,
+                          left: int = -1, right: int = 0, scale: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """:func:`paged_decode_fp8_fa_` for any N * group, in place: a chunked prefill, a prefix-cache
+    hit followed by the rest of the prompt, or wide-group tree decoding against a cache kept as fp8
+    byte pages.  The arguments, the cache types (``torch.float8_e4m3fn`` or ``torch.uint8``; anything
+    else is a TypeError), the scales (one float32 per KV slab, None: 1.0), the mask, the empty-row
+    rule and the table rules are paged_decode_fp8_fa_'s; the row order and the split are
+    paged_prefill_fa_'s.  The byte pools are never gathered or widened.
+    page_size % 16 == 0, Q and O bf16 / fp16 (FlashAttentionError otherwise).
+    A contiguous (Nk, d, B) byte cache with Nk % 16 == 0 is the pool with page_size = Nk,
+    num_pages = B and block_table[0, b] = b."""
+    for t in (O, l, m, Q, K8_pages, V8_pages):
+        _require(t.dim() == 3, "paged_prefill_fp8_fa! expects 3-D arrays: (N, d, batch) and (page_size, d, num_pages)")
+    _fp8_cache(K8_pages, "K8_pages"), _fp8_cache(V8_pages, "V8_pages")
+    group = int(group)
+    _require(group >= 1, "DimensionMismatch: group must be >= 1")
+    N, d, BG = Q.shape
+    ps, dv, P = K8_pages.shape[0], V8_pages.shape[1], K8_pages.shape[2]
+    _require(BG % group == 0, f"Q has batch {BG}, not a multiple of group {group}")
+    B = BG // group
+    _require(ps >= 1 and P >= 1, "DimensionMismatch: page_size and num_pages must be >= 1")
+    _require(K8_pages.shape == (ps, d, P), f"K8_pages has shape {tuple(K8_pages.shape)}, expected ({ps}, {d}, {P})")
+    _require(V8_pages.shape == (ps, dv, P), f"V8_pages has shape {tuple(V8_pages.shape)}, expected ({ps}, {dv}, {P})")
+    bt = _block_table(block_table, B, Q.device)
+    max_pages = bt.shape[0]
+    _require(O.shape == (N, dv, BG), f"O has shape {tuple(O.shape)}, expected ({N}, {dv}, {BG})")
+    _require(l.shape == (N, 1, BG) and m.shape == (N, 1, BG), "l, m must be (N, 1, batch * group)")
+    _require(l.dtype == torch.float32 and m.dtype == torch.float32, "l, m must be float32")
+    for s, name in ((k_scale, "k_scale"), (v_scale, "v_scale")):
+        _require(s is None or len(s) == B, f"DimensionMismatch: {name} must hold {B} scales, one per KV slab")
+    code = _dtype_code(Q, O)
+    cap = max_pages * ps
+    _masked_extents("prefill", N, cap)
+    _device_check(Q, K8_pages, V8_pages, O, l, m, bt)
+    ql = _lens(q_lens, N, B, Q.device, "q_lens")
+    kl = _lens(k_lens, cap, B, Q.device, "k_lens")
+    ks = _kv_scale(k_scale, B, Q.device, "k_scale")
+    vs = _kv_scale(v_scale, B, Q.device, "v_scale")
+    Lb = lib()
+    nws = Lb.fa_prefill_paged_fp8_fwd_workspace(code, N, d, dv, B, group, ps, max_pages)
+    ws = _workspace(Q.device, nws) if nws else None
+    _check(Lb.fa_prefill_paged_fp8_fwd(code, _ptr(Q), _ptr(K8_pages), _ptr(V8_pages), _ptr(ks), _ptr(vs), _ptr(bt),
+                                       _ptr(O), _ptr(l), _ptr(m), N, d, dv, B, group, ps, P, max_pages, _ptr(ql), _ptr(kl),
+                                       int(left), int(right), float(scale), _ptr(ws), int(nws), _stream(Q)))
+    return O, l, m
+
+
+def paged_prefill_fp8_fa(q: torch.Tensor, k8_pages: torch.Tensor, v8_pages: torch.Tensor, block_table: torch.Tensor,
+                         k_scale=None, v_scale=None, k_lens=None, q_lens=None, group: int = 1, left: int = -1,
+                         right: int = 0, scale: float = 0.0):
+    """``paged_prefill_fp8_fa(q, k8_pages, v8_pages, block_table, k_scale, v_scale, k_lens, q_lens, group,
+    left, right) -> (O, l, m)``: :func:`paged_prefill_fp8_fa_` on fresh outputs.  q (N, d, B*group),
+    k8_pages (page_size, d, num_pages), v8_pages (page_size, dv, num_pages), block_table (max_pages, B)."""
+    _require(q.dim() == 3 and k8_pages.dim() == 3 and v8_pages.dim() == 3,
+             "paged_prefill_fp8_fa expects 3-D arrays: (N, d, batch) and (page_size, d, num_pages)")
+    N, _, BG = q.shape
+    O = jl_empty((N, v8_pages.shape[1], BG), q.dtype, q.device)
+    l = jl_empty((N, 1, BG), torch.float32, q.device)
+    m = jl_empty((N, 1, BG), torch.float32, q.device)
+    return paged_prefill_fp8_fa_(O, l, m, q, k8_pages, v8_pages, block_table, k_scale, v_scale, k_lens, q_lens, group,
+                                 left, right, scale)
 
 
 # ----------------------------------------------------------------------------

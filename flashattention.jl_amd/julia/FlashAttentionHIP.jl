@@ -719,6 +719,50 @@ function paged_decode_fp8_fa(Q::ROCArray{T,3}, K8_pages::ROCArray{UInt8,3}, V8_p
     return paged_decode_fp8_fa!(O, l, m, Q, K8_pages, V8_pages, block_table; kw...)
 end
 
+# paged_prefill_fp8_fa!(O, l, m, Q, K8_pages, V8_pages, block_table; k_scale, v_scale, k_lens, q_lens,
+# group, left, right) — paged_decode_fp8_fa! for any N * group: a chunked prefill over the paged fp8
+# cache.  Arguments, scales and table rules as paged_decode_fp8_fa! (0-BASED page ids), row order
+# and split as paged_prefill_fa!.  page_size % 16 == 0.  A contiguous (Nk, d, B) byte cache is the
+# pool with page_size = Nk and block_table = Int32[0 1 … B-1].
+function paged_prefill_fp8_fa!(O::ROCArray{T,3}, l::ROCArray{Float32,3}, m::ROCArray{Float32,3},
+                               Q::ROCArray{T,3}, K8_pages::ROCArray{UInt8,3}, V8_pages::ROCArray{UInt8,3},
+                               block_table::ROCArray{Int32,2};
+                               k_scale=nothing, v_scale=nothing, k_lens=nothing, q_lens=nothing, group::Integer=1,
+                               left::Integer=-1, right::Integer=0) where {T}
+    N, d, BG = size(Q)
+    ps, dv, P = size(K8_pages, 1), size(V8_pages, 2), size(K8_pages, 3)
+    max_pages, B = size(block_table)
+    group >= 1 && BG == B * group || throw(DimensionMismatch("Q must hold group query slabs per KV slab"))
+    size(K8_pages) == (ps, d, P) || throw(DimensionMismatch("K8_pages"))
+    size(V8_pages) == (ps, dv, P) || throw(DimensionMismatch("V8_pages"))
+    size(O) == (N, dv, BG) || throw(DimensionMismatch("O"))
+    size(l) == (N, 1, BG) && size(m) == (N, 1, BG) || throw(DimensionMismatch("l, m must be (N, 1, batch * group)"))
+    nws = ccall((:fa_prefill_paged_fp8_fwd_workspace, libfa_hip), Csize_t,
+                (Cint, Int64, Int64, Int64, Int64, Int64, Int64, Int64), fa_dtype(T), N, d, dv, B, group, ps, max_pages)
+    GC.@preserve q_lens k_lens k_scale v_scale block_table with_workspace(nws) do ws
+        fa_check(ccall((:fa_prefill_paged_fp8_fwd, libfa_hip), Cint,
+                       (Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Cint}, Ptr{Cvoid},
+                        Ptr{Float32}, Ptr{Float32}, Int64, Int64, Int64, Int64, Int64, Int64, Int64, Int64, Ptr{Cint},
+                        Ptr{Cint}, Int64, Int64, Cfloat, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+                       fa_dtype(T), Q, K8_pages, V8_pages, scale_ptr(k_scale, B), scale_ptr(v_scale, B),
+                       Base.unsafe_convert(Ptr{Cint}, pointer(block_table)), O, l, m, N, d, dv, B, Int64(group), ps, P,
+                       max_pages, lens_ptr(q_lens, B), lens_ptr(k_lens, B), Int64(left), Int64(right), 0f0, ws, nws,
+                       stream_ptr()))
+    end
+    return O, l, m
+end
+
+# paged_prefill_fp8_fa(Q, K8_pages, V8_pages, block_table; k_scale, v_scale, k_lens, q_lens, group, left,
+# right) -> (O, l, m)
+function paged_prefill_fp8_fa(Q::ROCArray{T,3}, K8_pages::ROCArray{UInt8,3}, V8_pages::ROCArray{UInt8,3},
+                              block_table::ROCArray{Int32,2}; kw...) where {T}
+    N, BG = size(Q, 1), size(Q, 3)
+    O = similar(Q, N, size(V8_pages, 2), BG)
+    l = similar(Q, Float32, N, 1, BG)
+    m = similar(Q, Float32, N, 1, BG)
+    return paged_prefill_fp8_fa!(O, l, m, Q, K8_pages, V8_pages, block_table; kw...)
+end
+
 # varlen_fa_backward(Q, K, V, O, dO, l, m; q_lens, k_lens, left, right) -> (dQ, dK, dV): the
 # two-pass form, bitwise reproducible; exact zeros past the lengths and on empty rows
 function varlen_fa_backward(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3},

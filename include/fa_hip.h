@@ -637,6 +637,56 @@ int fa_prefill_paged_fwd(int dtype,
 size_t fa_prefill_paged_fwd_workspace(int dtype, int64_t N, int64_t d, int64_t dv, int64_t batch,
                                       int64_t group, int64_t page_size, int64_t max_pages);
 
+/* Chunked PREFILL attention over a PAGED fp8 KV cache: fa_decode_paged_fp8_fwd without its row
+ * limit, for a serving stack that keeps its cache as fp8 byte pages and runs a chunked prefill, a
+ * prefix-cache hit followed by the rest of the prompt, or tree decoding with N * group > 32.  The
+ * argument list is fa_decode_paged_fp8_fwd's and the contract is the union of two:
+ * from fa_prefill_paged_fwd, any N >= 1 and group >= 1 (N * group <= 32 included), the row order,
+ * the mask with off = nk - nq, the empty-row rule (O = +0, l = 0, m = -Inf by select),
+ * cap = max_pages * page_size in the role of Nk, the table rules (entry (j, b) read only for
+ * j < ceil(nk_b / page_size), every entry clamped to [0, num_pages) before it forms an address),
+ * shared pages, forward only, bf16 / fp16 Q and O (`dtype`), d and dv up to 128;
+ * from fa_decode_paged_fp8_fwd, K8_pages (page_size, d, num_pages) and V8_pages (page_size, dv,
+ * num_pages) of OCP e4m3fn BYTES, element (row t, feature f, page p) at t + page_size * (f + d * p);
+ * k_scale and v_scale DEVICE pointers to `batch` floats, one per KV slab, NULL meaning 1.0, finite
+ * and > 0, never read on the host; s_ij = scale * ks * (q_i . k8_j), O = vs * sum_j P_ij v8_j, ks
+ * folded into the score scale, vs applied once where O is normalised, no element multiplied by a
+ * scale; and the padding rule: rows of a slab's last page past nk_b may hold any byte except 0x7F
+ * and 0xFF, pages that no read entry names and entries past ceil(nk_b / page_size) anything.
+ * A contiguous (Nk, d, batch) byte cache with Nk % 16 == 0 is the pool with page_size = Nk,
+ * num_pages = batch, max_pages = 1 and block_table[0, b] = b.
+ * Checks, in order, all before any launch: null pointers (block_table is required; the scales
+ * may be NULL); DimensionMismatch (group, page_size, num_pages or max_pages below 1 included);
+ * FA_ERR_UNSUPPORTED for head dims, cap < N, dtype, page_size % 16 != 0 (a 16-B chunk of 16 keys
+ * must lie in one page), K8_pages or V8_pages not 16-B aligned; the kernels' 32-bit extents (one
+ * page below 2^31 bytes, cap below 2^31, the N * group rows of a KV slab times max(d, dv) below
+ * 2^30 elements; the pools have no size limit); the workspace.  N == 0 or batch == 0 is a no-op
+ * that dereferences nothing.
+ * The cache is never copied, gathered or widened: the bytes are staged in LDS as bytes and
+ * converted (exactly) in registers before the MFMAs.  The rows of a KV slab, position-major, are
+ * cut into blocks of 128 that share each key tile through LDS; page_size % 64 == 0 runs the
+ * instantiation that stages a tile by LDS-DMA through one descriptor per tile, every other
+ * multiple of 16 the one whose threads look up the page of each 16-B chunk of 16 keys.  Small
+ * grids split the keys (workspace: fp32 partials, merged in split order): no atomics, all three
+ * outputs bitwise reproducible and independent of where the pages lie, m the same bits for every
+ * split count. */
+int fa_prefill_paged_fp8_fwd(int dtype,
+                             const void* Q, const void* K8_pages, const void* V8_pages,
+                             const float* k_scale, const float* v_scale,
+                             const int* block_table,
+                             void* O, float* l, float* m,
+                             int64_t N, int64_t d, int64_t dv, int64_t batch, int64_t group,
+                             int64_t page_size, int64_t num_pages, int64_t max_pages,
+                             const int* q_lens, const int* k_lens,
+                             int64_t left, int64_t right,
+                             float scale, void* workspace, size_t workspace_bytes,
+                             void* hip_stream);
+
+/* Workspace bytes fa_prefill_paged_fp8_fwd needs: 0 unless the keys are split, then the fp32
+ * partials [nsplit][batch * group][N][dv + 2] (+ 256). */
+size_t fa_prefill_paged_fp8_fwd_workspace(int dtype, int64_t N, int64_t d, int64_t dv, int64_t batch,
+                                          int64_t group, int64_t page_size, int64_t max_pages);
+
 /* Standalone fused softmax, replaces
  *   fused_softmax!(P, S; dims)   reference src/fused_softmax.jl:1-41
  * (device versions src/cuda/fused_softmax.jl:11-314).  S, P: (M, N, batch)

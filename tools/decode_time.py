@@ -1,7 +1,7 @@
 """Decode attention against varlen attention on decode shapes: forward device time, one process,
 one run (tools/varlen_time.py's method).
 
-    python tools/decode_time.py [--window-s 0.05] [--windows 5] [--fp8 | --paged | --paged-fp8 | --prefill]
+    python tools/decode_time.py [--window-s 0.05] [--windows 5] [--fp8 | --paged | --paged-fp8 | --prefill | --prefill-fp8]
 
 Per shape (bf16, d = dv = 128, the causal window (-1, 0), nq queries per slab, B KV slabs, G query
 heads per KV slab, a cache of Nk keys) and per draw of the cache lengths (all full; a fixed-seed
@@ -48,6 +48,12 @@ outside the timed region.  Outputs are cross-checked.  Per row: median [min, max
 two ratios, the achieved TFLOP/s of the new kernel and of varlen alone over the visible-pair
 FLOPs 2 (d + dv) B G (N context + N (N + 1) / 2), and whether the new path beats "today" by more
 than the sum of the two spreads (max - min); nothing about the times is asserted.
+
+--prefill-fp8 times chunked prefill over the paged fp8 cache: fa_prefill_paged_fp8_fwd on byte pools
+(e4m3fn of normal draws, scales of 1.0 passed as device arrays) on --prefill's grid, against
+"today", widening the byte pools to 16-bit pools in torch (one pass, exact) and fa_prefill_paged_fwd,
+all timed, and against "16-bit alone", fa_prefill_paged_fwd on pools widened beforehand.  Outputs
+are cross-checked against 16-bit alone; the same columns and verdict as --prefill.
 """
 from __future__ import annotations
 
@@ -373,6 +379,79 @@ def prefill_leg(a, L, g, code, left, right):
                     del Q, K, V, KP, VP, KR, VR
 
 
+def prefill_fp8_leg(a, L, g, code, left, right):
+    P = lambda t: ctypes.c_void_p(t.data_ptr())
+    dt = torch.bfloat16
+    G = 8
+    print("prefill fp8: fa_prefill_paged_fp8_fwd on byte pools (G = 8, shuffled tables) against today = widening the byte pools to "
+          "16-bit pools in torch + fa_prefill_paged_fwd (all timed) and against fa_prefill_paged_fwd alone on pools widened "
+          "beforehand", flush=True)
+    for B in (1, 8):
+        for N in (8, 512, 2048):
+            for ctx in (8192, 32768):
+                for ps in (16, 64):
+                    nk = ctx + N
+                    mp = -(-nk // ps)
+                    cap = mp * ps
+                    mk = lambda n, b: torch.randn((n, D, b), generator=g, device="cuda")
+                    Q = fa_hip.jl_tensor(mk(N, B * G), dt)
+                    K8, V8 = (fa_hip.jl_tensor(mk(cap, B).to(torch.float8_e4m3fn).view(torch.uint8), torch.uint8) for _ in range(2))
+                    gp = torch.Generator(device="cuda").manual_seed(ps)
+                    (KP8, T), (VP8, _) = scatter(K8, ps, gp), scatter(V8, ps, gp.manual_seed(ps))
+                    # one pass: read the bytes, write twice as many (exact; the scales are 1.0)
+                    widen = lambda t: fa_hip.jl_empty(tuple(t.shape), dt).copy_(t.view(torch.float8_e4m3fn))
+                    KP, VP = widen(KP8), widen(VP8)
+                    ONE = torch.ones(B, dtype=torch.float32, device="cuda")
+                    mko = lambda: fa_hip.jl_empty((N, D, B * G), dt)
+                    O, OT, OV = mko(), mko(), mko()
+                    l, m = fa_hip.jl_empty((N, 1, B * G)), fa_hip.jl_empty((N, 1, B * G))
+                    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+                    nw = max(L.fa_prefill_paged_fwd_workspace(code, N, D, D, B, G, ps, mp), 1)
+                    assert L.fa_prefill_paged_fp8_fwd_workspace(code, N, D, D, B, G, ps, mp) in (0, nw)
+                    ws = torch.empty(nw, dtype=torch.uint8, device="cuda")
+                    KL = torch.full((B,), nk, dtype=torch.int32, device="cuda")
+
+                    def new():
+                        rc = L.fa_prefill_paged_fp8_fwd(code, P(Q), P(KP8), P(VP8), P(ONE), P(ONE), P(T), P(O), P(l), P(m), N, D, D,
+                                                        B, G, ps, KP8.shape[2], mp, None, P(KL), left, right, 0.0, P(ws), nw, st)
+                        assert rc == 0, L.fa_last_error()
+
+                    def wide(Kc=KP, Vc=VP, Oc=OV):
+                        rc = L.fa_prefill_paged_fwd(code, P(Q), P(Kc), P(Vc), P(T), P(Oc), P(l), P(m), N, D, D, B, G, ps,
+                                                    Kc.shape[2], mp, None, P(KL), left, right, 0.0, P(ws), nw, st)
+                        assert rc == 0, L.fa_last_error()
+
+                    def today():
+                        wide(widen(KP8), widen(VP8), OT)
+
+                    runs = [("new", new), ("today", today), ("16-bit alone", wide)]
+                    reps = {}
+                    for nm, fn in runs:
+                        for _ in range(2):
+                            fn()
+                        torch.cuda.synchronize()
+                        reps[nm] = max(3, min(20000, int(a.window_s / window(fn, 3)) + 1))
+                    top = float(OV.float().abs().max())
+                    for what, o in (("new", O), ("today", OT)):
+                        diff = float((o.float() - OV.float()).abs().max())
+                        assert diff <= top / 64, f"{what} and 16-bit outputs disagree: {diff} against max |O| {top}"
+                    times = {nm: [] for nm, _ in runs}
+                    for _ in range(a.windows):
+                        for nm, fn in runs:
+                            times[nm].append(window(fn, reps[nm]))
+                    med = {k: statistics.median(v) for k, v in times.items()}
+                    sp = {k: max(v) - min(v) for k, v in times.items()}
+                    flops = 2.0 * (D + D) * B * G * (N * ctx + N * (N + 1) / 2)
+                    cell = lambda nm: f"{nm} {med[nm]*1e6:9.1f} us [{min(times[nm])*1e6:.1f}, {max(times[nm])*1e6:.1f}]"
+                    beats = med["today"] - med["new"] > sp["today"] + sp["new"]
+                    print(f"B {B} N {N:4d} context {ctx:5d} page {ps:2d}: " + "  ".join(cell(nm) for nm, _ in runs) +
+                          f"  today / new {med['today']/med['new']:7.2f}  16-bit alone / new {med['16-bit alone']/med['new']:5.2f}  "
+                          f"TFLOP/s new {flops/med['new']*1e-12:6.1f} 16-bit alone {flops/med['16-bit alone']*1e-12:6.1f}  "
+                          f"{'beats today by more than the spreads' if beats else 'DOES NOT BEAT today by more than the spreads'}",
+                          flush=True)
+                    del Q, K8, V8, KP8, VP8, KP, VP
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--window-s", type=float, default=0.05)
@@ -381,6 +460,7 @@ def main():
     ap.add_argument("--paged", action="store_true")
     ap.add_argument("--paged-fp8", action="store_true")
     ap.add_argument("--prefill", action="store_true")
+    ap.add_argument("--prefill-fp8", action="store_true")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a ROCm device"
     L = fa_hip.lib()
@@ -390,7 +470,7 @@ def main():
     code = fa_hip.DTYPES[dt]
     left, right = -1, 0
     print(f"device: {torch.cuda.get_device_name(0)}; {a.windows} interleaved windows of {a.window_s} s; bf16, d = dv = {D}, "
-          f"window ({left}, {right})" + ("" if a.fp8 or a.paged or a.paged_fp8 or a.prefill else
+          f"window ({left}, {right})" + ("" if a.fp8 or a.paged or a.paged_fp8 or a.prefill or a.prefill_fp8 else
           "; the varlen baseline of G > 1 runs on a cache repeated G times outside the timed region"), flush=True)
     if a.fp8:
         return fp8_leg(a, L, g, code, left, right)
@@ -400,6 +480,8 @@ def main():
         return paged_fp8_leg(a, L, g, code, left, right)
     if a.prefill:
         return prefill_leg(a, L, g, code, left, right)
+    if a.prefill_fp8:
+        return prefill_fp8_leg(a, L, g, code, left, right)
     missed = []
     for (N, B, G, Nk) in SHAPES:
         mk = lambda n, b: fa_hip.jl_tensor(torch.randn((n, D, b), generator=g, device="cuda"), dt)
