@@ -18,6 +18,7 @@
 #include "fa_decode_plan.h"   // the decode plan (host functions)
 #include "fa_dense_plan.h"   // the dense plans (host functions)
 #include "fa_internal.h"
+#include "fa_kv_append_plan.h"   // the cache writers' plans (host functions)
 #include "fa_windowed.h"   // the windowed plans (host functions; no kernel is instantiated here)
 
 namespace {
@@ -1008,6 +1009,100 @@ int fa_prefill_paged_fp8_fwd(int dtype, const void* Q, const void* K8_pages, con
                              k_scale, v_scale, block_table, page_size, num_pages, max_pages};
     const char* why = "";
     const int rc = fa::launch_prefill_paged_fp8_fwd(a, (hipStream_t)hip_stream, &why);
+    return rc == FA_OK ? ok() : fail(rc, fn, why);
+}
+
+// The cache writers (fa_kv_append.hip).  fa_kv_append_paged and fa_kv_append_paged_fp8 share their
+// checks: the paged readers' order with the sources in the place of Q (pointers, dimensions,
+// head dims, cap < N, dtype, page size, alignment, extents); the lengths, the table and the scales
+// are device data and are not looked at here.
+static int kv_append_checked(const char* fn, bool fp8, int dtype, const void* K_new, const void* V_new, void* K_pages,
+                             void* V_pages, const float* k_scale, const float* v_scale, const int32_t* block_table, int64_t N,
+                             int64_t d, int64_t dv, int64_t batch, int64_t page_size, int64_t num_pages, int64_t max_pages,
+                             const int32_t* q_lens, const int32_t* k_lens, void* hip_stream) {
+    if (!valid_dtype(dtype)) return fail(FA_ERR_INVALID_ARG, fn, "unknown dtype");
+    if (N == 0 || batch == 0) return ok();   // no row: nothing to write, nothing dereferenced
+    if (!K_new || !V_new || !K_pages || !V_pages || !block_table) return fail(FA_ERR_INVALID_ARG, fn, "null pointer");
+    if (N < 0 || d < 1 || dv < 1 || batch < 0 || page_size < 1 || num_pages < 1 || max_pages < 1)
+        return fail(FA_ERR_INVALID_ARG, fn,
+                    "DimensionMismatch: N, batch must be >= 0 and d, dv, page_size, num_pages, max_pages >= 1");
+    if (d > fa::kMaxHeadDim || dv > fa::kMaxHeadDim)
+        return fail(FA_ERR_UNSUPPORTED, fn, "head dimension exceeds the compiled maximum (128)");
+    // cap = max_pages * page_size, saturated: the 32-bit check below refuses what would overflow
+    const int64_t cap = max_pages > INT64_MAX / page_size ? INT64_MAX : max_pages * page_size;
+    if (cap < N) return fail(FA_ERR_UNSUPPORTED, fn, "cache append needs max_pages * page_size >= N (a row would have no place)");
+    if (!fa::dense_16bit(dtype))
+        return fail(FA_ERR_UNSUPPORTED, fn, fp8 ? "fp8 cache append is bf16 / fp16 only (K_new and V_new; the pools are e4m3fn)"
+                                                : "cache append is bf16 / fp16 only");
+    if (page_size % (fp8 ? 16 : 8) != 0)
+        return fail(FA_ERR_UNSUPPORTED, fn,
+                    fp8 ? "fp8 cache append needs page_size % 16 == 0 (a 16-B chunk of 16 keys lies in one page)"
+                        : "cache append needs page_size % 8 == 0 (a 16-B chunk of 8 keys lies in one page)");
+    if (!fa::aligned16(K_pages) || !fa::aligned16(V_pages))
+        return fail(FA_ERR_UNSUPPORTED, fn, "cache append needs 16-B aligned page pools");
+    // one page and one (N, dim) source slab within 2^31 bytes, the logical keys within an int; the
+    // pools and the sources as a whole have no limit: page and slab bases are 64-bit
+    const int64_t dmax = d > dv ? d : dv;
+    if (page_size > INT32_MAX || page_size * dmax >= (int64_t)INT32_MAX / (fp8 ? 1 : 2) || cap >= (int64_t)INT32_MAX ||
+        N >= (int64_t)INT32_MAX / (2 * dmax) || batch > INT32_MAX)
+        return fail(FA_ERR_UNSUPPORTED, fn, "extent exceeds the kernels' 32-bit addressing");
+    const fa::KvAppendPlan pl = fa::kv_append_plan(fp8, N, d, dv, batch, page_size, max_pages);
+    if (pl.grid > INT32_MAX) return fail(FA_ERR_UNSUPPORTED, fn, "extent exceeds the kernels' 32-bit addressing");
+    const fa::KvAppendArgs a{dtype, fp8, K_new, V_new, K_pages, V_pages, k_scale, v_scale, block_table, N, d, dv, batch,
+                             page_size, num_pages, max_pages, q_lens, k_lens};
+    const char* why = "";
+    const int rc = fa::launch_kv_append(a, (hipStream_t)hip_stream, &why);
+    return rc == FA_OK ? ok() : fail(rc, fn, why);
+}
+
+// Not part of the public header (tests): fa::kv_append_plan.  out: {decode, pages, nseg, feats, nfsplit, grid}.
+int fa_debug_kv_append_plan(int fp8, int64_t N, int64_t d, int64_t dv, int64_t batch, int64_t page_size, int64_t max_pages,
+                            int64_t* out) {
+    if (N < 1 || d < 1 || dv < 1 || batch < 1 || page_size < 1 || page_size % (fp8 ? 16 : 8) != 0 || max_pages < 1) return -1;
+    const fa::KvAppendPlan pl = fa::kv_append_plan(fp8 != 0, N, d, dv, batch, page_size, max_pages);
+    if (out) {
+        out[0] = pl.decode; out[1] = pl.pages; out[2] = pl.nseg; out[3] = pl.feats; out[4] = pl.nfsplit; out[5] = pl.grid;
+    }
+    return pl.decode;
+}
+
+int fa_kv_append_paged(int dtype, const void* K_new, const void* V_new, void* K_pages, void* V_pages,
+                       const int32_t* block_table, int64_t N, int64_t d, int64_t dv, int64_t batch, int64_t page_size,
+                       int64_t num_pages, int64_t max_pages, const int32_t* q_lens, const int32_t* k_lens, void* hip_stream) {
+    return kv_append_checked("fa_kv_append_paged", false, dtype, K_new, V_new, K_pages, V_pages, nullptr, nullptr, block_table,
+                             N, d, dv, batch, page_size, num_pages, max_pages, q_lens, k_lens, hip_stream);
+}
+
+int fa_kv_append_paged_fp8(int dtype, const void* K_new, const void* V_new, void* K8_pages, void* V8_pages,
+                           const float* k_scale, const float* v_scale, const int32_t* block_table, int64_t N, int64_t d,
+                           int64_t dv, int64_t batch, int64_t page_size, int64_t num_pages, int64_t max_pages,
+                           const int32_t* q_lens, const int32_t* k_lens, void* hip_stream) {
+    return kv_append_checked("fa_kv_append_paged_fp8", true, dtype, K_new, V_new, K8_pages, V8_pages, k_scale, v_scale,
+                             block_table, N, d, dv, batch, page_size, num_pages, max_pages, q_lens, k_lens, hip_stream);
+}
+
+// fa_kv_quantize_fp8: pointers, dimensions, dtype, the 32-bit extent of a slab, the workspace.
+size_t fa_kv_quantize_fp8_workspace(int dtype, int64_t Nk, int64_t d, int64_t dv, int64_t batch) {
+    return fa::kv_quant_plan(dtype, Nk, d, dv, batch).total;
+}
+
+int fa_kv_quantize_fp8(int dtype, const void* K, const void* V, void* K8, void* V8, float* k_scale, float* v_scale, int64_t Nk,
+                       int64_t d, int64_t dv, int64_t batch, void* workspace, size_t workspace_bytes, void* hip_stream) {
+    const char* const fn = "fa_kv_quantize_fp8";
+    if (!valid_dtype(dtype)) return fail(FA_ERR_INVALID_ARG, fn, "unknown dtype");
+    if (Nk == 0 || batch == 0) return ok();   // no element: nothing to write, nothing dereferenced
+    if (!K || !V || !K8 || !V8 || !k_scale || !v_scale) return fail(FA_ERR_INVALID_ARG, fn, "null pointer");
+    if (Nk < 0 || d < 1 || dv < 1 || batch < 0)
+        return fail(FA_ERR_INVALID_ARG, fn, "DimensionMismatch: Nk, batch must be >= 0 and d, dv >= 1");
+    if (!fa::dense_16bit(dtype)) return fail(FA_ERR_UNSUPPORTED, fn, "cache quantisation is bf16 / fp16 only (the result is e4m3fn)");
+    const fa::KvQuantPlan pl = fa::kv_quant_plan(dtype, Nk, d, dv, batch);
+    if (pl.parts < 1 || batch > INT32_MAX / pl.parts)
+        return fail(FA_ERR_UNSUPPORTED, fn, "extent exceeds the kernels' 32-bit addressing");
+    if (!workspace || workspace_bytes < pl.total)
+        return fail(FA_ERR_WORKSPACE, fn, "workspace missing or smaller than fa_kv_quantize_fp8_workspace()");
+    const fa::KvQuantArgs a{dtype, K, V, K8, V8, k_scale, v_scale, Nk, d, dv, batch, workspace, workspace_bytes};
+    const char* why = "";
+    const int rc = fa::launch_kv_quantize_fp8(a, (hipStream_t)hip_stream, &why);
     return rc == FA_OK ? ok() : fail(rc, fn, why);
 }
 

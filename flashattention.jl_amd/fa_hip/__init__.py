@@ -47,6 +47,7 @@ __all__ = [
     "decode_fa", "decode_fa_", "decode_fp8_fa", "decode_fp8_fa_", "quantize_kv_fp8",
     "paged_decode_fa", "paged_decode_fa_", "paged_kv_gather", "paged_decode_fp8_fa", "paged_decode_fp8_fa_",
     "paged_prefill_fa", "paged_prefill_fa_", "paged_prefill_fp8_fa", "paged_prefill_fp8_fa_",
+    "paged_kv_append_", "paged_kv_append_fp8_", "quantize_kv_fp8_hip",
     "fused_softmax", "fused_softmax_", "DTYPES",
 ]
 
@@ -249,6 +250,18 @@ def lib() -> ctypes.CDLL:
         L.fa_debug_prefill_paged_fp8_plan.restype = ctypes.c_int
         L.fa_debug_prefill_paged_fp8_plan.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64, i64, i64, ctypes.c_int,
                                                       ctypes.POINTER(i64)]
+    if hasattr(L, "fa_kv_append_paged"):
+        L.fa_kv_append_paged.restype = ctypes.c_int
+        L.fa_kv_append_paged.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, vp, vp, vp]
+        L.fa_kv_append_paged_fp8.restype = ctypes.c_int
+        L.fa_kv_append_paged_fp8.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64,
+                                             vp, vp, vp]
+        L.fa_kv_quantize_fp8_workspace.restype = ctypes.c_size_t
+        L.fa_kv_quantize_fp8_workspace.argtypes = [ctypes.c_int, i64, i64, i64, i64]
+        L.fa_kv_quantize_fp8.restype = ctypes.c_int
+        L.fa_kv_quantize_fp8.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, ctypes.c_size_t, vp]
+        L.fa_debug_kv_append_plan.restype = ctypes.c_int
+        L.fa_debug_kv_append_plan.argtypes = [ctypes.c_int, i64, i64, i64, i64, i64, i64, ctypes.POINTER(i64)]
     L.fa_softmax_workspace.restype = ctypes.c_size_t
     L.fa_softmax_workspace.argtypes = [i64, i64, i64, ctypes.c_int]
     L.fa_softmax.restype = ctypes.c_int
@@ -1312,6 +1325,88 @@ def paged_prefill_fp8_fa(q: torch.Tensor, k8_pages: torch.Tensor, v8_pages: torc
     m = jl_empty((N, 1, BG), torch.float32, q.device)
     return paged_prefill_fp8_fa_(O, l, m, q, k8_pages, v8_pages, block_table, k_scale, v_scale, k_lens, q_lens, group,
                                  left, right, scale)
+
+
+# ----------------------------------------------------------------------------
+# the cache writers: new rows into a paged cache, 16-bit or fp8, and a contiguous cache to fp8
+# (fa_kv_append_paged, fa_kv_append_paged_fp8, fa_kv_quantize_fp8)
+# ----------------------------------------------------------------------------
+def _paged_kv_append(name, fp8, k_pages, v_pages, block_table, k_new, v_new, k_scale, v_scale, k_lens, q_lens):
+    for t in (k_pages, v_pages, k_new, v_new):
+        _require(t.dim() == 3, f"{name} expects 3-D arrays: (N, d, batch) and (page_size, d, num_pages)")
+    if fp8:
+        _fp8_cache(k_pages, "k8_pages"), _fp8_cache(v_pages, "v8_pages")
+    N, d, B = k_new.shape
+    ps, dv, P = k_pages.shape[0], v_pages.shape[1], k_pages.shape[2]
+    _require(ps >= 1 and P >= 1, "DimensionMismatch: page_size and num_pages must be >= 1")
+    _require(k_pages.shape == (ps, d, P), f"k_pages has shape {tuple(k_pages.shape)}, expected ({ps}, {d}, {P})")
+    _require(v_pages.shape == (ps, dv, P), f"v_pages has shape {tuple(v_pages.shape)}, expected ({ps}, {dv}, {P})")
+    _require(v_new.shape == (N, dv, B), f"v_new has shape {tuple(v_new.shape)}, expected ({N}, {dv}, {B})")
+    bt = _block_table(block_table, B, k_new.device)
+    max_pages = bt.shape[0]
+    for s, sname in ((k_scale, "k_scale"), (v_scale, "v_scale")):
+        _require(s is None or len(s) == B, f"DimensionMismatch: {sname} must hold {B} scales, one per KV slab")
+    code = _dtype_code(k_new, v_new) if fp8 else _dtype_code(k_new, v_new, k_pages, v_pages)
+    cap = max_pages * ps
+    _device_check(k_new, v_new, k_pages, v_pages, bt)
+    ql = _lens(q_lens, N, B, k_new.device, "q_lens")
+    kl = _lens(k_lens, cap, B, k_new.device, "k_lens")
+    Lb = lib()
+    if fp8:
+        ks = _kv_scale(k_scale, B, k_new.device, "k_scale")
+        vs = _kv_scale(v_scale, B, k_new.device, "v_scale")
+        _check(Lb.fa_kv_append_paged_fp8(code, _ptr(k_new), _ptr(v_new), _ptr(k_pages), _ptr(v_pages), _ptr(ks), _ptr(vs),
+                                         _ptr(bt), N, d, dv, B, ps, P, max_pages, _ptr(ql), _ptr(kl), _stream(k_new)))
+    else:
+        _check(Lb.fa_kv_append_paged(code, _ptr(k_new), _ptr(v_new), _ptr(k_pages), _ptr(v_pages), _ptr(bt), N, d, dv, B,
+                                     ps, P, max_pages, _ptr(ql), _ptr(kl), _stream(k_new)))
+    return k_pages, v_pages
+
+
+def paged_kv_append_(k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
+                     k_new: torch.Tensor, v_new: torch.Tensor, k_lens=None, q_lens=None):
+    """``paged_kv_append_(k_pages, v_pages, block_table, k_new, v_new, k_lens, q_lens) -> (k_pages,
+    v_pages)``: write the rows of k_new (N, d, B) and v_new (N, dv, B) into the paged cache, in
+    place.  The lengths are the ones the attention call that follows takes (:func:`paged_prefill_fa`
+    with group = 1 on the KV side): k_lens the lengths AFTER the append (None: max_pages *
+    page_size), q_lens the new rows per slab (None: N); new row i < q_lens[b] becomes logical key
+    k_lens[b] - q_lens[b] + i of slab b.  Only the written elements change, bit for bit the source's;
+    no pool byte is read.  The pages one slab writes must not be named by another slab's written
+    range.  page_size % 8 == 0, bf16 / fp16 (FlashAttentionError otherwise)."""
+    return _paged_kv_append("paged_kv_append!", False, k_pages, v_pages, block_table, k_new, v_new, None, None, k_lens, q_lens)
+
+
+def paged_kv_append_fp8_(k8_pages: torch.Tensor, v8_pages: torch.Tensor, block_table: torch.Tensor,
+                         k_new: torch.Tensor, v_new: torch.Tensor, k_scale=None, v_scale=None, k_lens=None, q_lens=None):
+    """:func:`paged_kv_append_` into pools of e4m3fn bytes (``torch.float8_e4m3fn`` or
+    ``torch.uint8``; anything else is a TypeError): each written byte is
+    ``(x.float() / scale[b]).clamp(-448, 448)`` rounded to nearest even, bit for bit
+    :func:`quantize_kv_fp8`'s expression for the same scale.  k_scale, v_scale: one float32 per KV
+    slab (None: 1.0), finite and > 0.  k_new, v_new bf16 / fp16, page_size % 16 == 0."""
+    return _paged_kv_append("paged_kv_append_fp8!", True, k8_pages, v8_pages, block_table, k_new, v_new, k_scale, v_scale,
+                            k_lens, q_lens)
+
+
+def quantize_kv_fp8_hip(k: torch.Tensor, v: torch.Tensor):
+    """``quantize_kv_fp8_hip(k, v) -> (k8, v8, k_scale, v_scale)``: :func:`quantize_kv_fp8` as two
+    HIP kernels (fa_kv_quantize_fp8), bit for bit its result on the host: k (Nk, d, B), v (Nk, dv, B)
+    bf16 / fp16 on the device, one float32 scale per slab (amax / 448, 1.0 for an all-zero slab)."""
+    _require(k.dim() == 3 and v.dim() == 3, "quantize_kv_fp8_hip expects 3-D (Nk, d, batch) arrays")
+    Nk, d, B = k.shape
+    dv = v.shape[1]
+    _require(v.shape == (Nk, dv, B), f"v has shape {tuple(v.shape)}, expected ({Nk}, {dv}, {B})")
+    code = _dtype_code(k, v)
+    _device_check(k, v)
+    k8 = jl_empty(k.shape, torch.float8_e4m3fn, k.device)
+    v8 = jl_empty(v.shape, torch.float8_e4m3fn, v.device)
+    ks = torch.empty(B, dtype=torch.float32, device=k.device)
+    vs = torch.empty(B, dtype=torch.float32, device=k.device)
+    Lb = lib()
+    nws = Lb.fa_kv_quantize_fp8_workspace(code, Nk, d, dv, B)
+    ws = _workspace(k.device, nws) if nws else None
+    _check(Lb.fa_kv_quantize_fp8(code, _ptr(k), _ptr(v), _ptr(k8), _ptr(v8), _ptr(ks), _ptr(vs), Nk, d, dv, B,
+                                 _ptr(ws), int(nws), _stream(k)))
+    return k8, v8, ks, vs
 
 
 # ----------------------------------------------------------------------------

@@ -763,6 +763,72 @@ function paged_prefill_fp8_fa(Q::ROCArray{T,3}, K8_pages::ROCArray{UInt8,3}, V8_
     return paged_prefill_fp8_fa!(O, l, m, Q, K8_pages, V8_pages, block_table; kw...)
 end
 
+# paged_kv_append!(K_pages, V_pages, block_table, K_new, V_new; k_lens, q_lens) -> (K_pages, V_pages):
+# write the rows of K_new (N, d, B), V_new (N, dv, B) into the paged cache.  The lengths are the
+# ones the attention call that follows takes (k_lens AFTER the append); 0-BASED page ids.  Only the
+# written elements change; the pages one slab writes must not be named by another slab's range.
+function paged_kv_append!(K_pages::ROCArray{T,3}, V_pages::ROCArray{T,3}, block_table::ROCArray{Int32,2},
+                          K_new::ROCArray{T,3}, V_new::ROCArray{T,3}; k_lens=nothing, q_lens=nothing) where {T}
+    N, d, B = size(K_new)
+    ps, dv, P = size(K_pages, 1), size(V_pages, 2), size(K_pages, 3)
+    max_pages = size(block_table, 1)
+    size(block_table, 2) == B || throw(DimensionMismatch("block_table must be (max_pages, batch)"))
+    size(K_pages) == (ps, d, P) || throw(DimensionMismatch("K_pages"))
+    size(V_pages) == (ps, dv, P) || throw(DimensionMismatch("V_pages"))
+    size(V_new) == (N, dv, B) || throw(DimensionMismatch("V_new"))
+    GC.@preserve q_lens k_lens block_table begin
+        fa_check(ccall((:fa_kv_append_paged, libfa_hip), Cint,
+                       (Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cint}, Int64, Int64, Int64, Int64, Int64,
+                        Int64, Int64, Ptr{Cint}, Ptr{Cint}, Ptr{Cvoid}),
+                       fa_dtype(T), K_new, V_new, K_pages, V_pages, Base.unsafe_convert(Ptr{Cint}, pointer(block_table)),
+                       N, d, dv, B, ps, P, max_pages, lens_ptr(q_lens, B), lens_ptr(k_lens, B), stream_ptr()))
+    end
+    return K_pages, V_pages
+end
+
+# paged_kv_append_fp8!(K8_pages, V8_pages, block_table, K_new, V_new; k_scale, v_scale, k_lens, q_lens):
+# paged_kv_append! into pools of e4m3fn bytes, each byte (x / scale[b]) clamped to +-448 and rounded
+# to nearest even.  page_size % 16 == 0.
+function paged_kv_append_fp8!(K8_pages::ROCArray{UInt8,3}, V8_pages::ROCArray{UInt8,3}, block_table::ROCArray{Int32,2},
+                              K_new::ROCArray{T,3}, V_new::ROCArray{T,3};
+                              k_scale=nothing, v_scale=nothing, k_lens=nothing, q_lens=nothing) where {T}
+    N, d, B = size(K_new)
+    ps, dv, P = size(K8_pages, 1), size(V8_pages, 2), size(K8_pages, 3)
+    max_pages = size(block_table, 1)
+    size(block_table, 2) == B || throw(DimensionMismatch("block_table must be (max_pages, batch)"))
+    size(K8_pages) == (ps, d, P) || throw(DimensionMismatch("K8_pages"))
+    size(V8_pages) == (ps, dv, P) || throw(DimensionMismatch("V8_pages"))
+    size(V_new) == (N, dv, B) || throw(DimensionMismatch("V_new"))
+    GC.@preserve q_lens k_lens k_scale v_scale block_table begin
+        fa_check(ccall((:fa_kv_append_paged_fp8, libfa_hip), Cint,
+                       (Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Cint}, Int64,
+                        Int64, Int64, Int64, Int64, Int64, Int64, Ptr{Cint}, Ptr{Cint}, Ptr{Cvoid}),
+                       fa_dtype(T), K_new, V_new, K8_pages, V8_pages, scale_ptr(k_scale, B), scale_ptr(v_scale, B),
+                       Base.unsafe_convert(Ptr{Cint}, pointer(block_table)), N, d, dv, B, ps, P, max_pages,
+                       lens_ptr(q_lens, B), lens_ptr(k_lens, B), stream_ptr()))
+    end
+    return K8_pages, V8_pages
+end
+
+# quantize_kv_fp8(K, V) -> (K8, V8, k_scale, v_scale): a (Nk, d, B) / (Nk, dv, B) cache as e4m3fn
+# bytes with one Float32 scale per slab, amax / 448 (1 for an all-zero slab)
+function quantize_kv_fp8(K::ROCArray{T,3}, V::ROCArray{T,3}) where {T}
+    Nk, d, B = size(K)
+    dv = size(V, 2)
+    size(V) == (Nk, dv, B) || throw(DimensionMismatch("V"))
+    K8, V8 = similar(K, UInt8, Nk, d, B), similar(V, UInt8, Nk, dv, B)
+    k_scale, v_scale = similar(K, Float32, B), similar(K, Float32, B)
+    nws = ccall((:fa_kv_quantize_fp8_workspace, libfa_hip), Csize_t, (Cint, Int64, Int64, Int64, Int64),
+                fa_dtype(T), Nk, d, dv, B)
+    with_workspace(nws) do ws
+        fa_check(ccall((:fa_kv_quantize_fp8, libfa_hip), Cint,
+                       (Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Int64, Int64,
+                        Int64, Int64, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+                       fa_dtype(T), K, V, K8, V8, k_scale, v_scale, Nk, d, dv, B, ws, nws, stream_ptr()))
+    end
+    return K8, V8, k_scale, v_scale
+end
+
 # varlen_fa_backward(Q, K, V, O, dO, l, m; q_lens, k_lens, left, right) -> (dQ, dK, dV): the
 # two-pass form, bitwise reproducible; exact zeros past the lengths and on empty rows
 function varlen_fa_backward(Q::ROCArray{T,3}, K::ROCArray{T,3}, V::ROCArray{T,3},

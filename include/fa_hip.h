@@ -687,6 +687,86 @@ int fa_prefill_paged_fp8_fwd(int dtype,
 size_t fa_prefill_paged_fp8_fwd_workspace(int dtype, int64_t N, int64_t d, int64_t dv, int64_t batch,
                                           int64_t group, int64_t page_size, int64_t max_pages);
 
+/* WRITE new K / V rows into a PAGED 16-bit KV cache: the first half of a decode step ("put this
+ * token's K and V into their pages, then attend") and of a chunked prefill.  The arguments mean
+ * what they mean for fa_prefill_paged_fwd, with group = 1 on the KV side: the append and the
+ * attention call that follows it take the same (q_lens, k_lens); k_lens is the length AFTER the
+ * append.  K_new (N, d, batch), V_new (N, dv, batch); K_pages (page_size, d, num_pages), V_pages
+ * (page_size, dv, num_pages), element (row t, feature f, page p) at t + page_size * (f + d * p);
+ * block_table (max_pages, batch) int32 on the device.
+ * Per slab b: nq = clamp(q_lens[b], 0, N), nk = clamp(k_lens[b], 0, cap), cap = max_pages *
+ * page_size, clamped on the device and never read on the host (NULL = N, cap).  New row i < nq is
+ * the key at logical position j = nk - nq + i, the position the prefill's mask gives query i, and
+ * goes to row j % page_size of page clamp(block_table[j / page_size, b], 0, num_pages - 1), for
+ * every feature of K and of V.  Rows i >= nq and rows with j < 0 (nk < nq) are not written.  A table
+ * entry is read only for a page that the written range [max(nk - nq, 0), nk) touches.
+ * Guarantees: every written element is bitwise the source element; every other byte of both pools
+ * is bitwise unchanged; no pool byte is read (no read-modify-write of neighbours); no access
+ * leaves the pools or the (N, ., batch) sources, whatever the table and the lengths hold; each
+ * destination element is written once, so the result is bitwise reproducible; no atomics, no
+ * workspace, no allocation, no synchronisation.
+ * The caller's business: the pages in one slab's written range must not be named by another
+ * slab's written range in the same call (copy-on-write of shared prefixes happens outside the
+ * library).  If they are, the values in those pages are unspecified; safety still holds.
+ * Checks, in order, all before any launch: null pointers (K_new, V_new, both pools and block_table
+ * are required, the lengths may be NULL); DimensionMismatch (d, dv, page_size, num_pages or
+ * max_pages below 1, negative N or batch); FA_ERR_UNSUPPORTED for head dims above
+ * fa_max_head_dim(), cap < N, a dtype other than bf16 / fp16, page_size % 8 != 0, pools that are
+ * not 16-B aligned; the 32-bit extents (one page below 2^31 bytes, cap below 2^31, one source
+ * slab below 2^31 bytes).  N == 0 or batch == 0 is a no-op that dereferences nothing.  K_new and
+ * V_new may start at any element-aligned address.
+ * The work is split by destination: a workgroup owns (slab, touched page, feature range), looks
+ * its page up once, stages the source runs through LDS and stores 16-B destination-aligned
+ * chunks, the ragged head and tail as narrower stores of exactly the owned elements.  N == 1 (the
+ * decode step) runs one thread per feature of K and of V, several slabs per workgroup. */
+int fa_kv_append_paged(int dtype,
+                       const void* K_new, const void* V_new,
+                       void* K_pages, void* V_pages,
+                       const int* block_table,
+                       int64_t N, int64_t d, int64_t dv, int64_t batch,
+                       int64_t page_size, int64_t num_pages, int64_t max_pages,
+                       const int* q_lens, const int* k_lens,
+                       void* hip_stream);
+
+/* fa_kv_append_paged into pools of OCP e4m3fn BYTES: K8_pages (page_size, d, num_pages), V8_pages
+ * (page_size, dv, num_pages), as fa_decode_paged_fp8_fwd and fa_prefill_paged_fp8_fwd read them.
+ * `dtype` is the type of K_new and V_new (bf16 / fp16).  k_scale, v_scale: DEVICE pointers to
+ * `batch` floats, one per slab, NULL meaning 1.0, finite and > 0, never read on the host.  The
+ * written byte is e4m3fn_rne(clamp(float(x) / s_b, -448, 448)): an IEEE fp32 division (not a
+ * multiplication by a reciprocal), round-to-nearest-even onto the e4m3fn grid, subnormals and the
+ * sign of zero included: bit for bit what the float32 expression
+ * (x.float() / s).clamp(-448, 448) converted to float8_e4m3fn gives on the host.  Sources are
+ * finite or +-Inf (Inf saturates to +-448); NaN sources are outside the contract.  Everything else
+ * is fa_kv_append_paged's, with page_size % 16 != 0 refused, as the fp8 readers refuse it. */
+int fa_kv_append_paged_fp8(int dtype,
+                           const void* K_new, const void* V_new,
+                           void* K8_pages, void* V8_pages,
+                           const float* k_scale, const float* v_scale,
+                           const int* block_table,
+                           int64_t N, int64_t d, int64_t dv, int64_t batch,
+                           int64_t page_size, int64_t num_pages, int64_t max_pages,
+                           const int* q_lens, const int* k_lens,
+                           void* hip_stream);
+
+/* A contiguous 16-bit cache as e4m3fn bytes with one scale per slab: K (Nk, d, batch), V (Nk, dv,
+ * batch) of `dtype` (bf16 / fp16) to K8, V8 (bytes, the same shapes) and k_scale, v_scale (`batch`
+ * floats each, device).  Per slab amax = max |x| (exact, order-free), s = amax > 0 ? amax / 448 :
+ * 1, and every byte is fa_kv_append_paged_fp8's expression with that s.  Two kernels: the first
+ * writes the maxima of fixed spans of each slab to the workspace, the second reduces its slab's
+ * maxima, writes the scale and converts.  No atomics, bitwise reproducible.  Sources finite.
+ * Checks, in order: null pointers, DimensionMismatch (d or dv below 1, negative Nk or batch),
+ * FA_ERR_UNSUPPORTED for a dtype other than bf16 / fp16 and for a slab of 2^31 bytes or more,
+ * FA_ERR_WORKSPACE.  Nk == 0 or batch == 0 is a no-op that dereferences nothing (no scale is
+ * written). */
+int fa_kv_quantize_fp8(int dtype, const void* K, const void* V,
+                       void* K8, void* V8, float* k_scale, float* v_scale,
+                       int64_t Nk, int64_t d, int64_t dv, int64_t batch,
+                       void* workspace, size_t workspace_bytes, void* hip_stream);
+
+/* Workspace bytes fa_kv_quantize_fp8 needs: the spans' maxima, [2][batch][parts] floats (+ 256);
+ * 0 for a shape it refuses or for which it does nothing. */
+size_t fa_kv_quantize_fp8_workspace(int dtype, int64_t Nk, int64_t d, int64_t dv, int64_t batch);
+
 /* Standalone fused softmax, replaces
  *   fused_softmax!(P, S; dims)   reference src/fused_softmax.jl:1-41
  * (device versions src/cuda/fused_softmax.jl:11-314).  S, P: (M, N, batch)
